@@ -1,7 +1,22 @@
 """Throughput of the k-mer x filter probe path on MI355X (driver contract).
 
     python bench.py [--gpus N --steps K --warmup W] [--workload species|genus|mlst|multigenus]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run does what the headline figure needs and no more: it builds the
+bank and the reads, warms up, times the K steps (HIP events around every
+probe give the roofline figures of those same steps), checks the last step's
+k-mer total, writes the last step's outputs with --dump-outputs, and prints
+the result line.  --full adds the legs that take runs of their own: `checks`
+(the C oracle on a sample of the reads, the totals), `host_path`,
+`end_to_end` and `cpu_baseline`; in a plain run those fields are null.
+
+--dump-outputs DIR writes what the last timed step left in the caller's
+buffers as DIR/<name>.npy (dump_outputs: the hit rows of a fixed, seeded
+sample of the reads, their k-mer counts, the per-doc totals).  Genomes and
+reads are seeded, so two builds run with the same arguments see the same
+inputs and their dumps compare array for array.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment (no torchrun around
 it), bench.py starts the N ranks itself (launch_ranks: one child process per
@@ -21,7 +36,7 @@ over RCCL: reads sharded (seed 42+rank), bank replicated, weak scaling; at
 N > 1 each rank takes 12.5M reads by default, so N=8 is BASELINE.json
 configs[2] (config 3: 100M reads over 8 GPUs) at its stated size.
 
-Every rank checks its own values after the timed region (`checks`): its hit
+With --full every rank checks its own values after the timed region (`checks`): its hit
 rows of 3,000 reads against the C oracle, its local totals against its hit
 matrix, and (rank 0) the all-reduced totals against the host sum of the
 all-gathered per-rank totals; multigenus checks its exchanged column blocks
@@ -45,7 +60,8 @@ filter word (h or K per k-mer).  The direct kernels: one 128-byte L2 line fill p
 k-mer and doc group; rbloom: K dwords per k-mer; MLST: the 64-byte rows
 themselves, its banks being Infinity-Cache resident).  Both + the read bytes,
 hit matrix and per-read metadata; peak = 8.0 TB/s; traffic = PMC bytes per
-probe from profiles/r06_traffic.json.  cpu_baseline: the C oracle (oracle/liboracle.so,
+probe from profiles/r06_traffic.json.  The remaining legs run under --full
+only.  cpu_baseline: the C oracle (oracle/liboracle.so,
 OpenMP) on a bounded sample of the same reads and bank (rank 0, N=1 only);
 its hits are also compared with the GPU's; plus the reference's per-read loop
 shape on one core.  host_path: the same step from host buffers (PCIe).
@@ -109,6 +125,13 @@ def parse():
     ap.add_argument("--hashes", type=int, default=7, help="species/multigenus: COBS num_hashes (default 7)")
     ap.add_argument("--mlst-foreign", type=float, default=0.0,
                     help="mlst: fraction of reads from outside every locus (WGS-like input: ~1.0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the oracle and totals checks, the "
+                         "PCIe-inclusive host path, the end-to-end file legs and the CPU baseline "
+                         "(each still has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (sampled hit rows, k-mer counts, totals) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU baseline time")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--check-reads", type=int, default=3000,
@@ -516,8 +539,10 @@ def main():
         assert int(tot[-1]) == want, f"k-mer total {int(tot[-1])} != {want}"
     if args.workload == "genus":  # member k-mers / sampled k-mers (steers the rbloom probe path)
         wl.config["member_fraction"] = round(int(tot[0]) / max(1, int(tot[-1])), 4)
-    # every rank checks its own values (oracle sample, totals, exchanged columns); outside the timed region
-    checks = self_check(wl, args, rank, world, dev, pg)
+    if args.dump_outputs:  # before any later leg queries into the same buffers again
+        dump_outputs(wl, args, Path(args.dump_outputs), rank, world)
+    # --full: every rank checks its own values (oracle sample, totals, exchanged columns); outside the timed region
+    checks = self_check(wl, args, rank, world, dev, pg) if args.full else None
 
     value = wl.probes_per_step() * args.steps / elapsed
     from xspect2_amd._lib import XS_PATH_PARTITIONED
@@ -593,13 +618,13 @@ def main():
         # the PMC files are one-GPU, 1M-read measurements: they describe no rank of this run
         traffic, lookup_l2 = None, None
     # the PCIe-inclusive legs are a per-GPU figure: measured at N=1 only
-    host = None if args.no_host_path or world > 1 else host_path(wl, args)
+    host = None if not args.full or args.no_host_path or world > 1 else host_path(wl, args)
     e2e = None
-    if rank == 0 and world == 1 and not args.no_e2e and args.workload in ("species", "genus"):
+    if args.full and rank == 0 and world == 1 and not args.no_e2e and args.workload in ("species", "genus"):
         e2e = end_to_end(wl, args)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(wl, args)
 
     nr = f"{wl.n / 1e6:g}M x {args.read_len}bp reads"
@@ -670,8 +695,57 @@ def main():
         b.close()
     if pg:
         dist.destroy_process_group()
-    if not checks["ok"]:
+    if checks is not None and not checks["ok"]:
         sys.exit(3)
+
+
+# --dump-outputs: bytes of sampled hit rows, all banks together (the whole dump stays under 64 MB)
+DUMP_HIT_BYTES = 48 << 20
+
+
+def dump_outputs(wl, args, out_dir: Path, rank: int, world: int) -> None:
+    """The last timed step's outputs, as a caller of the device path holds
+    them, written as <out_dir>/<name>.npy (names end in _rank<r> at N > 1):
+
+    * sample_rows: the reads whose rows are kept, ascending; every read when
+      the hit matrices fit DUMP_HIT_BYTES, else a seeded sample without
+      replacement, the same for the same arguments (float64);
+    * hits_bank<i>: those rows of bank i's [reads, docs] hit matrix (float32:
+      a count is at most a read's k-mers; float64 from 2^24 k-mers per read;
+      absent under --totals-only, which writes no matrix);
+    * kmers_per_read: those reads' k-mer counts (float64);
+    * totals_bank<i>: bank i's D+1 totals, all-reduced at N > 1 (float64);
+    * exchanged / exchanged_rows (multigenus in a process group): sampled
+      rows of this rank's [reads / N, all banks' docs] matrix.
+    """
+    import torch
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    hit_dt = np.float32 if wl.nk_read < (1 << 24) else np.float64
+    item = np.dtype(hit_dt).itemsize
+
+    def sample(n, row_cells, seed):
+        m = min(n, max(1, DUMP_HIT_BYTES // (row_cells * item + 16)))  # + the row's index and k-mer count
+        if m == n:
+            return np.arange(n, dtype=np.int64)
+        return np.sort(np.random.default_rng(seed).choice(n, m, replace=False)).astype(np.int64)
+
+    def rows_of(t, rows):  # gathered on the device: only the sample crosses PCIe
+        return t[torch.from_numpy(rows).to(t.device)].cpu().numpy()
+
+    exchanged = getattr(wl, "exchanged", None)
+    rows = sample(wl.n, sum(wl.docs) + (exchanged.shape[1] if exchanged is not None else 0), 20240)
+    np.save(out_dir / f"sample_rows{tag}.npy", rows.astype(np.float64))
+    np.save(out_dir / f"kmers_per_read{tag}.npy", rows_of(wl.d_nk, rows).astype(np.float64))
+    for i, (h, t) in enumerate(zip(wl.d_hits, wl.d_tot)):
+        if not args.totals_only:
+            np.save(out_dir / f"hits_bank{i}{tag}.npy", rows_of(h, rows).astype(hit_dt))
+        np.save(out_dir / f"totals_bank{i}{tag}.npy", t.cpu().numpy().astype(np.float64))
+    if exchanged is not None:
+        xrows = sample(exchanged.shape[0], sum(wl.docs) + exchanged.shape[1], 20241)
+        np.save(out_dir / f"exchanged_rows{tag}.npy", xrows.astype(np.float64))
+        np.save(out_dir / f"exchanged{tag}.npy", rows_of(exchanged, xrows).astype(hit_dt))
 
 
 def oracle_banks(wl):

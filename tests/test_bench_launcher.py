@@ -147,3 +147,68 @@ def test_block_checksum_sees_moved_and_changed_cells():
     if not torch.equal(z, x):
         assert bench._checksum(z, 1000) != base
     assert bench._checksum(x, 999) != base
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """A plain run has no extra legs; --full and --dump-outputs are there to ask for them."""
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def _dump_workload(n, docs, seed):
+    """The buffers dump_outputs reads, on the CPU: hits, k-mer counts, totals."""
+    import types
+
+    import torch
+    rng = np.random.default_rng(seed)
+    hits = [torch.from_numpy(rng.integers(0, 131, (n, d)).astype(np.int32)) for d in docs]
+    return types.SimpleNamespace(
+        n=n, docs=docs, nk_read=130, d_hits=hits,
+        d_nk=torch.from_numpy(rng.integers(0, 131, n).astype(np.int64)),
+        d_tot=[torch.cat([h.sum(0, dtype=torch.int64), torch.tensor([130 * n])]) for h in hits])
+
+
+def test_dump_outputs_writes_the_buffers_as_float_arrays(tmp_path):
+    """Small outputs are written whole, in float32 / float64, value for value;
+    --totals-only leaves the hit matrices out."""
+    import types
+    wl = _dump_workload(500, [7, 3], seed=1)
+    args = types.SimpleNamespace(totals_only=False)
+    bench.dump_outputs(wl, args, tmp_path / "a", 0, 1)
+    got = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["hits_bank0.npy", "hits_bank1.npy", "kmers_per_read.npy", "sample_rows.npy",
+                           "totals_bank0.npy", "totals_bank1.npy"]
+    assert np.array_equal(got["sample_rows.npy"], np.arange(500))
+    for i in range(2):
+        assert got[f"hits_bank{i}.npy"].dtype == np.float32
+        assert np.array_equal(got[f"hits_bank{i}.npy"], wl.d_hits[i].numpy())
+        assert got[f"totals_bank{i}.npy"].dtype == np.float64
+        assert np.array_equal(got[f"totals_bank{i}.npy"], wl.d_tot[i].numpy())
+    assert got["kmers_per_read.npy"].dtype == np.float64
+    assert np.array_equal(got["kmers_per_read.npy"], wl.d_nk.numpy())
+    bench.dump_outputs(wl, types.SimpleNamespace(totals_only=True), tmp_path / "b", 1, 2)
+    assert sorted(f.name for f in (tmp_path / "b").iterdir()) == [
+        "kmers_per_read_rank1.npy", "sample_rows_rank1.npy", "totals_bank0_rank1.npy", "totals_bank1_rank1.npy"]
+
+
+def test_dump_outputs_samples_large_outputs_the_same_way_every_time(tmp_path, monkeypatch):
+    """Past the byte budget a seeded sample of the rows is kept: the same rows
+    on every run, ascending, without repeats, and the files within the budget."""
+    import types
+    monkeypatch.setattr(bench, "DUMP_HIT_BYTES", 10_000)
+    wl = _dump_workload(2000, [9], seed=2)
+    args = types.SimpleNamespace(totals_only=False)
+    bench.dump_outputs(wl, args, tmp_path / "a", 0, 1)
+    bench.dump_outputs(wl, args, tmp_path / "b", 0, 1)
+    rows = np.load(tmp_path / "a" / "sample_rows.npy").astype(np.int64)
+    assert 0 < rows.size < 2000 and np.all(np.diff(rows) > 0) and rows[-1] < 2000
+    assert rows.size * (9 * 4 + 16) <= 10_000 < (rows.size + 1) * (9 * 4 + 16)
+    assert np.array_equal(np.load(tmp_path / "a" / "hits_bank0.npy"), wl.d_hits[0].numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "kmers_per_read.npy"), wl.d_nk.numpy()[rows])
+    for f in (tmp_path / "a").iterdir():
+        assert (tmp_path / "b" / f.name).read_bytes() == f.read_bytes()

@@ -23,8 +23,8 @@ XSPECT_SHARE_GPU=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 
 timeout -k 10 300 python tools/sharded_classify.py check --root $R --world 2 > $F/check.json 2>&1 || { cat $F/check.json; exit 16; }
 cat $F/check.json; cat $F/single.log $F/shard.log | grep -E "s$|Saved" | tail -4
 echo "== bench: config 3 per-GPU shard (12.5 M reads)"
-timeout -k 10 900 python -u bench.py --reads 12500000 --steps 5 --warmup 2 --no-host-path > $F/bench_c3.json 2> $F/bench_c3.err || { tail -30 $F/bench_c3.err; exit 17; }
+timeout -k 10 900 python -u bench.py --full --reads 12500000 --steps 5 --warmup 2 --no-host-path > $F/bench_c3.json 2> $F/bench_c3.err || { tail -30 $F/bench_c3.err; exit 17; }
 cut -c1-400 $F/bench_c3.json
 echo "== bench: default (config 2) with the host path"
-timeout -k 10 600 python -u bench.py > $F/bench_c2.json 2> $F/bench_c2.err || { tail -30 $F/bench_c2.err; exit 19; }
+timeout -k 10 600 python -u bench.py --full > $F/bench_c2.json 2> $F/bench_c2.err || { tail -30 $F/bench_c2.err; exit 19; }
 cut -c1-600 $F/bench_c2.json

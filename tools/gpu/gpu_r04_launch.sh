@@ -6,9 +6,9 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 F=gpurun_out/r04launch; mkdir -p $F
-XSPECT_BENCH_SHARE_GPU=1 timeout -k 10 400 python3 -u bench.py --gpus 2 --steps 5 --warmup 2 --launch-timeout 360 > $F/species_n2.json 2> $F/species_n2.err || { tail -30 $F/species_n2.err; exit 10; }
+XSPECT_BENCH_SHARE_GPU=1 timeout -k 10 400 python3 -u bench.py --full --gpus 2 --steps 5 --warmup 2 --launch-timeout 360 > $F/species_n2.json 2> $F/species_n2.err || { tail -30 $F/species_n2.err; exit 10; }
 cut -c1-600 $F/species_n2.json
-XSPECT_BENCH_SHARE_GPU=1 timeout -k 10 400 python3 -u bench.py --gpus 2 --workload multigenus --steps 5 --warmup 2 --launch-timeout 360 > $F/multigenus_n2.json 2> $F/multigenus_n2.err || { tail -30 $F/multigenus_n2.err; exit 11; }
+XSPECT_BENCH_SHARE_GPU=1 timeout -k 10 400 python3 -u bench.py --full --gpus 2 --workload multigenus --steps 5 --warmup 2 --launch-timeout 360 > $F/multigenus_n2.json 2> $F/multigenus_n2.err || { tail -30 $F/multigenus_n2.err; exit 11; }
 cut -c1-300 $F/multigenus_n2.json
 timeout -k 10 120 python3 -u -c "
 import sys; sys.path.insert(0, '.')

@@ -21,13 +21,13 @@ if [ "$1" = "1" ]; then
   tail -1 $F/smoke.log
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $F/gpu_tests.log 2>&1 || { tail -40 $F/gpu_tests.log; exit 11; }
   tail -2 $F/gpu_tests.log
-  timeout -k 10 600 python -u bench.py > $F/species.json 2> $F/species.err || { tail -30 $F/species.err; exit 12; }
+  timeout -k 10 600 python -u bench.py --full > $F/species.json 2> $F/species.err || { tail -30 $F/species.err; exit 12; }
   line $F/species.json
-  timeout -k 10 600 python -u bench.py --workload genus > $F/genus.json 2> $F/genus.err || { tail -30 $F/genus.err; exit 13; }
+  timeout -k 10 600 python -u bench.py --full --workload genus > $F/genus.json 2> $F/genus.err || { tail -30 $F/genus.err; exit 13; }
   line $F/genus.json
-  timeout -k 10 600 python -u bench.py --workload mlst > $F/mlst.json 2> $F/mlst.err || { tail -30 $F/mlst.err; exit 14; }
+  timeout -k 10 600 python -u bench.py --full --workload mlst > $F/mlst.json 2> $F/mlst.err || { tail -30 $F/mlst.err; exit 14; }
   line $F/mlst.json
-  timeout -k 10 900 python -u bench.py --reads 12500000 --steps 5 --warmup 2 --no-host-path > $F/config3_shard.json 2> $F/config3_shard.err || { tail -30 $F/config3_shard.err; exit 15; }
+  timeout -k 10 900 python -u bench.py --full --reads 12500000 --steps 5 --warmup 2 --no-host-path > $F/config3_shard.json 2> $F/config3_shard.err || { tail -30 $F/config3_shard.err; exit 15; }
   line $F/config3_shard.json
   cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$F/trace" -o run -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-host-path --no-e2e > "$GRAFT_REPO_ROOT/$F/trace_bench.json" 2> "$GRAFT_REPO_ROOT/$F/trace.err" || { tail -20 "$GRAFT_REPO_ROOT/$F/trace.err"; exit 16; }
   cd "$GRAFT_REPO_ROOT" && f=$(find $F/trace -name "*kernel_stats.csv" | head -1) && cp $f $F/kernel_stats.csv && rm -f $(find $F/trace -name "*kernel_trace.csv")
@@ -47,9 +47,9 @@ elif [ "$1" = "2" ]; then
   python3 tools/pmc_kernels.py $P "species, partitioned COBS at round-6 HEAD" $P/pmc.json > /dev/null
   python3 -c "import json; d=json.load(open('$P/pmc.json')); print('species hbm_bytes_per_step', d['hbm_bytes_per_step'] / 1e9)"
   rm -rf $P/p*/
-  XSPECT_BENCH_SHARE_GPU=1 timeout -k 10 900 python -u bench.py --gpus 2 --steps 5 --warmup 2 > $F/n2_config3_share.json 2> $F/n2_config3_share.err || { tail -30 $F/n2_config3_share.err; exit 31; }
-  timeout -k 10 600 python -u bench.py --rccl-world1 --reads 12500000 --steps 3 --warmup 1 --no-host-path --no-e2e --no-cpu-baseline > $F/rccl1_config3.json 2> $F/rccl1_config3.err || { tail -30 $F/rccl1_config3.err; exit 32; }
-  timeout -k 10 600 python -u bench.py --rccl-world1 --workload multigenus --steps 3 --warmup 1 --no-host-path --no-cpu-baseline > $F/rccl1_multigenus.json 2> $F/rccl1_multigenus.err || { tail -30 $F/rccl1_multigenus.err; exit 33; }
+  XSPECT_BENCH_SHARE_GPU=1 timeout -k 10 900 python -u bench.py --full --gpus 2 --steps 5 --warmup 2 > $F/n2_config3_share.json 2> $F/n2_config3_share.err || { tail -30 $F/n2_config3_share.err; exit 31; }
+  timeout -k 10 600 python -u bench.py --full --rccl-world1 --reads 12500000 --steps 3 --warmup 1 --no-host-path --no-e2e --no-cpu-baseline > $F/rccl1_config3.json 2> $F/rccl1_config3.err || { tail -30 $F/rccl1_config3.err; exit 32; }
+  timeout -k 10 600 python -u bench.py --full --rccl-world1 --workload multigenus --steps 3 --warmup 1 --no-host-path --no-cpu-baseline > $F/rccl1_multigenus.json 2> $F/rccl1_multigenus.err || { tail -30 $F/rccl1_multigenus.err; exit 33; }
   for f in n2_config3_share rccl1_config3 rccl1_multigenus; do
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[1], d['n_gpus'], d['dist_backend'], d['rccl_world'], d['value'], round(d['ms_per_step'],2), json.dumps(d['checks']))" $F/$f.json
   done

@@ -29,5 +29,5 @@ for k, v in d["kernels"].items():
     print(f"{k[:48]:48s} hbm {hb:6.2f} GB  req {v.get('TCC_REQ_sum', 0):.4g}  l2hit {v.get('l2_hit_rate', 0):.3f}  TCP_pend {v.get('TCP_PENDING_STALL_CYCLES_sum', 0):.3g}")
 print("hbm_bytes_per_step", d["hbm_bytes_per_step"] / 1e9)
 PY
-timeout -k 10 300 python -u bench.py --workload genus --no-host-path > $F/genus.json 2> $F/genus.err || { tail -30 $F/genus.err; exit 13; }
+timeout -k 10 300 python -u bench.py --full --workload genus --no-host-path > $F/genus.json 2> $F/genus.err || { tail -30 $F/genus.err; exit 13; }
 python3 -c "import json; d=json.loads(open('$F/genus.json').read().strip().splitlines()[-1]); r=d['roofline']; print(d['value'], d['ms_per_step'], d['checks']['ok'], r['probe_ms_avg'], r.get('pass_ms_avg'), r.get('frac'), r.get('traffic_frac'))"
