@@ -46,6 +46,7 @@
 #ifndef XSPECT_HIP_H
 #define XSPECT_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -272,6 +273,22 @@ int xs_bank_probe_rows(xs_bank* bank, uint64_t* rows);
 #define XS_PATH_GATHER 0
 #define XS_PATH_PARTITIONED 1
 int xs_bank_probe_path(const xs_bank* bank, int* path);
+
+/* Name of the probe kernel the last query on this handle launched, as a
+ * NUL-terminated string in buf ("" before the first query; XS_ERR_ARG when cap
+ * is too small, 32 bytes hold every name).  The direct COBS probe is one of
+ * many compiled instantiations, chosen by the bank's shape: "fast<21,7>"
+ * (k, h), "vslice<31,3>" (k or 0, groups), "wide<31,1,C4,G3>" (k, h or 0,0;
+ * chunk lanes; groups), "slots<0,0,8,2>" (k, h or 0,0; groups; chunks),
+ * "general"; "cobspart" is the partitioned COBS probe; rbloom banks report
+ * "bloom<21,7>", "bloom<0,0>" or "bloompart".  The name and the kernel come
+ * from one table entry, so tests can hold a bank shape to the kernel it is
+ * meant to exercise.  Measurement only: no effect on results. */
+int xs_bank_probe_kernel(const xs_bank* bank, char* buf, size_t cap);
+/* Every compiled direct COBS probe instantiation, one name per line
+ * (XS_ERR_ARG when cap is too small; 4096 bytes hold the list).  Needs no
+ * device. */
+int xs_probe_kernel_names(char* buf, size_t cap);
 
 /* Probe path selection of one handle.  The defaults (what xs_bank_open and
  * xs_bank_create_* set: 1, 1, 24576, 1) are the paths a production query takes;

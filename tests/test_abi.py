@@ -49,6 +49,22 @@ def test_version_and_errors_without_gpu():
     assert rc == _lib.XS_ERR_ARG
 
 
+def test_probe_kernel_names_without_gpu():
+    """xs_probe_kernel_names lists the compiled direct COBS probe instantiations
+    from the families' own tables (no device needed), in the forms
+    xs_bank_probe_kernel reports; a buffer that is too small is an argument
+    error, not a truncated list."""
+    from xspect2_amd import _lib
+    from xspect2_amd.bank import probe_kernel_names
+    names = probe_kernel_names()
+    assert len(names) == len(set(names)) == 57
+    form = re.compile(r"fast<\d+,\d+>|vslice<\d+,[1-4]>|wide<\d+,\d+,C(2|4|8|16),G[1-4]>|slots<\d+,\d+,\d+,\d+>|general")
+    assert all(form.fullmatch(n) for n in names), names
+    assert names[0] == "fast<21,7>" and names[-1] == "general"
+    buf = ctypes.create_string_buffer(16)
+    assert _lib.load().xs_probe_kernel_names(buf, len(buf)) == _lib.XS_ERR_ARG
+
+
 def test_product_does_not_import_oracle():
     """The product package never touches oracle/ (checker only)."""
     for py in (ROOT / "xspect2_amd").rglob("*.py"):

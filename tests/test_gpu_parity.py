@@ -71,11 +71,21 @@ CLASSIC_CASES = [
     (1100, 16, 3, [3_011]),   # wide kernel, 9 data chunks of 16 lanes, general (k, h)
     (2100, 21, 7, [4_001]),   # 17 chunks: general kernel
 ]
+# the kernel each comment above claims, as Bank.probe_kernel reports it (direct probe)
+CLASSIC_KERNELS = {
+    (200, 21, 7): "wide<21,7,C2,G1>",
+    (500, 31, 1): "wide<31,1,C4,G1>",
+    (700, 25, 5): "wide<0,0,C8,G1>",
+    (2048, 31, 1): "wide<31,1,C16,G1>",
+    (2000, 21, 7): "wide<21,7,C16,G1>",
+    (1100, 16, 3): "wide<0,0,C16,G1>",
+    (2100, 21, 7): "general",
+}
 
 
 @pytest.mark.parametrize("D,k,h,sig", CLASSIC_CASES)
 def test_classic_probe_matches_oracle(xs, oracle_mod, D, k, h, sig):
-    _classic_case(xs, oracle_mod, D, k, h, sig, opts={"cobs_part": 0})
+    _classic_case(xs, oracle_mod, D, k, h, sig, opts={"cobs_part": 0}, want_kernel=CLASSIC_KERNELS.get((D, k, h)))
 
 
 @pytest.mark.parametrize("D,k,h,sig", [c for c in CLASSIC_CASES if c[0] <= 128] + [(128, 21, 7, [70_001]),
@@ -140,7 +150,7 @@ def _opts(mode, ws_mb=None):
     return o
 
 
-def _classic_case(xs, oracle_mod, D, k, h, sig, want_path=None, opts=None):
+def _classic_case(xs, oracle_mod, D, k, h, sig, want_path=None, opts=None, want_kernel=None):
     ob, gb, seqs, _ = _pair(xs, oracle_mod, D, k, h, sig, seed=D * 31 + k)
     if opts:
         gb.set_probe_options(**opts)
@@ -157,6 +167,10 @@ def _classic_case(xs, oracle_mod, D, k, h, sig, want_path=None, opts=None):
         assert np.array_equal(got_h, want_h), _explain(got_h, want_h, reads)
         if want_path is not None:
             assert gb.probe_path() == want_path
+        if want_path == 1:
+            assert gb.probe_kernel() == "cobspart"
+        if want_kernel is not None:
+            assert gb.probe_kernel() == want_kernel
         tot, nk = gb.query_totals(reads, step=step)
         assert np.array_equal(tot, want_h.sum(axis=0, dtype=np.uint64))
         assert nk == int(want_n.sum())
@@ -234,6 +248,7 @@ def test_partitioned_default_on_bank_over_mall(xs, oracle_mod):
         gb.set_probe_options(cobs_part=2)
         got_h, got_n = gb.query(reads, step=step)
         assert gb.probe_path() == _lib.XS_PATH_PARTITIONED
+        assert gb.probe_kernel() == "cobspart"
         gb.set_probe_options(cobs_part=1)
         assert np.array_equal(got_n, want_n)
         assert np.array_equal(got_h, want_h), int((got_h != want_h).sum())
@@ -307,6 +322,7 @@ def test_vslice_probe_matches_oracle(xs, oracle_mod, D, k, G):
     for step in (1, 3):
         want_h, want_n = ob.query(reads, step=step)
         got_h, got_n = gb.query(reads, step=step)
+        assert gb.probe_kernel() == f"vslice<{31 if k == 31 else 0},{G}>"
         assert np.array_equal(got_n, want_n)
         assert np.array_equal(got_h, want_h), _explain(got_h, want_h, reads)
         tot, nk = gb.query_totals(reads, step=step)
@@ -452,6 +468,7 @@ def test_bloom_partitioned_random_configs(xs, oracle_mod, k, nbytes, K, seed):
         assert np.array_equal(got_n, want_n)
         assert np.array_equal(got_h[:, 0], want_h)
         assert gb.probe_path() == 1
+        assert gb.probe_kernel() == "bloompart"
         tot, nk = gb.query_totals(reads, step=step)
         assert int(tot[0]) == int(want_h.sum()) and nk == int(want_n.sum())
     gb.close()
@@ -1140,6 +1157,7 @@ def test_bloom_gather_random_configs(xs, oracle_mod, k, nbytes, K, seed):
         want_h, want_n = bf.query(reads, step=step)
         got_h, got_n = gb.query(reads, step=step)
         assert gb.probe_path() == 0
+        assert gb.probe_kernel() == ("bloom<21,7>" if (k, K) == (21, 7) else "bloom<0,0>")
         assert np.array_equal(got_n, want_n) and np.array_equal(got_h[:, 0], want_h)
         tot, nk = gb.query_totals(reads, step=step)
         assert int(tot[0]) == int(want_h.sum()) and nk == int(want_n.sum())

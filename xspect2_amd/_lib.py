@@ -152,6 +152,8 @@ SIGNATURES = {
     "xs_bank_probe_rows": (_int, [_vp, ctypes.POINTER(_u64)]),
     "xs_bank_pass_stats": (_int, [_vp, _vp, _vp]),
     "xs_bank_probe_path": (_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
+    "xs_bank_probe_kernel": (_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
+    "xs_probe_kernel_names": (_int, [ctypes.c_char_p, ctypes.c_size_t]),
     "xs_bank_set_probe_options": (_int, [_vp, ctypes.POINTER(ProbeOptions)]),
     "xs_bank_get_probe_options": (_int, [_vp, ctypes.POINTER(ProbeOptions)]),
     "xs_bank_workspace_bytes": (_int, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),

@@ -465,6 +465,14 @@ class Bank:
         check(load().xs_bank_probe_path(self.handle, ctypes.byref(v)))
         return int(v.value)
 
+    def probe_kernel(self) -> str:
+        """Name of the probe kernel the last query launched (xs_bank_probe_kernel):
+        "fast<21,7>", "vslice<31,3>", "wide<31,1,C4,G3>", "slots<0,0,8,2>", "general",
+        "cobspart", "bloom<21,7>", "bloom<0,0>", "bloompart"; "" before the first query."""
+        buf = ctypes.create_string_buffer(64)
+        check(load().xs_bank_probe_kernel(self.handle, buf, len(buf)))
+        return buf.value.decode()
+
     def workspace_bytes(self) -> tuple[int, int]:
         """(held, peak) device bytes of this handle's transient workspace
         (xs_bank_workspace_bytes; the bank image not included)."""
@@ -511,6 +519,14 @@ class Bank:
         self.close()
 
 
+def probe_kernel_names() -> list[str]:
+    """Every compiled direct COBS probe instantiation (xs_probe_kernel_names), in
+    the form Bank.probe_kernel reports."""
+    buf = ctypes.create_string_buffer(4096)
+    check(load().xs_probe_kernel_names(buf, len(buf)))
+    return buf.value.decode().split()
+
+
 def best_device(hits, n: int, num_docs: int, best, best_hits=None, stream: int | None = None) -> None:
     """xs_best_device: per-read best doc of a device hit matrix (n x num_docs uint32)."""
     check(load().xs_best_device(_dptr(hits), n, num_docs, _dptr(best), _dptr(best_hits), stream))
@@ -538,5 +554,5 @@ def _dptr(x) -> int | None:
     return ptr()
 
 
-__all__ = ["Bank", "bloom_parameters", "cobs_signature_size", "KIND_NAMES", "pinned_empty", "max_kmers",
+__all__ = ["Bank", "bloom_parameters", "cobs_signature_size", "KIND_NAMES", "pinned_empty", "max_kmers", "probe_kernel_names",
            "XS_BANK_COBS_CLASSIC", "XS_BANK_COBS_COMPACT", "XS_BANK_RBLOOM", "_lib"]

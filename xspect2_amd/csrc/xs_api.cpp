@@ -199,6 +199,7 @@ struct xs_bank {
     bool bloom_pending = false;
     double member_frac = 1.0;
     int last_path = XS_PATH_GATHER;
+    const char* last_kernel = "";    // name of the probe kernel the last query launched (a string literal)
     ProbeOptions opt;               // path selection (xs_bank_set_probe_options)
     PinnedBuf stage[3];             // D2H staging ring for large host outputs (d2h_pageable: 2, HitSink: 3)
     hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr};
@@ -793,6 +794,7 @@ int run_query(xs_bank* b, const Inputs& in, uint32_t step, uint32_t* d_hits, uin
     }
     BloomPartPlan plan;
     int path = XS_PATH_GATHER;
+    const char* kernel = "";
     // The partitioned path's workspace is transient: when HBM cannot hold it,
     // the query takes the gather path instead of failing.
     auto part_ws = [&]() -> bool {
@@ -807,6 +809,7 @@ int run_query(xs_bank* b, const Inputs& in, uint32_t step, uint32_t* d_hits, uin
     if (bloom && bloom_part_plan(b->bloom_view(), in.n, in.plan_bytes(), step, b->member_frac, b->opt, &plan) &&
         part_ws()) {
         path = XS_PATH_PARTITIONED;
+        kernel = "bloompart";
         const BloomPartWs ws{b->pk_nkc.as<uint64_t>(), b->pk_kofs.as<uint64_t>(), b->pk_scan.p, b->pk_scan.cap,
                              b->pk_entries.as<uint64_t>(), b->pk_tbl.as<uint16_t>(), b->pk_miss.as<uint32_t>(),
                              b->pk_aux.as<uint32_t>()};
@@ -814,20 +817,22 @@ int run_query(xs_bank* b, const Inputs& in, uint32_t step, uint32_t* d_hits, uin
         HIPCHK(launch_probe_bloom_part(rv, b->bloom_view(), plan, ws, d_hits, partials, blocks, s,
                                        b->profiling ? &rec : nullptr));
     } else if (b->kind == XS_BANK_RBLOOM) {
-        HIPCHK(launch_probe_bloom(rv, b->bloom_view(), d_hits, partials, blocks, s));
+        HIPCHK(launch_probe_bloom(rv, b->bloom_view(), d_hits, partials, blocks, s, &kernel));
     } else {
         const CobsView cv = b->cobs_view();
         if (cobs_part) {
             path = XS_PATH_PARTITIONED;
+            kernel = "cobspart";
             const PartWs ws{b->pk_nkc.as<uint64_t>(), b->pk_kofs.as<uint64_t>(), b->pk_scan.p, b->pk_scan.cap,
                             b->pk_entries.p, b->pk_tbl.as<uint16_t>(), b->pk_aux.as<uint32_t>()};
             PassRecorder rec{&b->pass_ev, &b->pass_tag, &b->pass_used};
             HIPCHK(launch_probe_cobs_part(rv, cv, cplan, ws, d_hits, partials, blocks, s, b->profiling ? &rec : nullptr));
         } else {
-            HIPCHK(launch_probe_cobs(rv, cv, d_hits, partials, blocks, s));
+            HIPCHK(launch_probe_cobs(rv, cv, d_hits, partials, blocks, s, &kernel));
         }
     }
     b->last_path = path;
+    b->last_kernel = kernel;
     if (timed) {
         HIPCHK(hipEventRecord(b->events[b->events_used].second, s));
         ++b->events_used;
@@ -1413,11 +1418,13 @@ int query_small(xs_bank* b, const char* seqs, const uint64_t* offsets, uint64_t 
     rv.step = step;
     rv.grab = 1;
     auto* d_part = reinterpret_cast<uint64_t*>(d + o_part);
-    if (bloom) HIPCHK(launch_probe_bloom(rv, b->bloom_view(), d_hits, d_part, blocks, s));
-    else HIPCHK(launch_probe_cobs(rv, b->cobs_view(), d_hits, d_part, blocks, s));
+    const char* kernel = "";
+    if (bloom) HIPCHK(launch_probe_bloom(rv, b->bloom_view(), d_hits, d_part, blocks, s, &kernel));
+    else HIPCHK(launch_probe_cobs(rv, b->cobs_view(), d_hits, d_part, blocks, s, &kernel));
     HIPCHK(hipMemcpyAsync(h + o_part, d + o_part, out_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     b->last_path = XS_PATH_GATHER;
+    b->last_kernel = kernel;
     const auto* part = reinterpret_cast<const uint64_t*>(h + o_part);
     std::vector<uint64_t> tot(pcols, 0);
     for (int i = 0; i < blocks; ++i)
@@ -2220,6 +2227,31 @@ int xs_bank_probe_path(const xs_bank* b, int* path) {
         std::lock_guard<std::mutex> lk(const_cast<xs_bank*>(b)->mu);  // after any query in flight on the handle
         *path = b->last_path;
         return XS_OK;
+    });
+}
+
+// Copies a NUL-terminated name (list) into the caller's buffer.
+static int copy_names(const char* src, size_t len, char* buf, size_t cap) {
+    if (len + 1 > cap) return fail(XS_ERR_ARG, "buffer too small");
+    memcpy(buf, src, len);
+    buf[len] = '\0';
+    return XS_OK;
+}
+
+int xs_bank_probe_kernel(const xs_bank* b, char* buf, size_t cap) {
+    return xs::guard([&]() -> int {
+        if (!b || !buf) return fail(XS_ERR_ARG, "null argument");
+        std::lock_guard<std::mutex> lk(const_cast<xs_bank*>(b)->mu);  // after any query in flight on the handle
+        return copy_names(b->last_kernel, strlen(b->last_kernel), buf, cap);
+    });
+}
+
+int xs_probe_kernel_names(char* buf, size_t cap) {
+    return xs::guard([&]() -> int {
+        if (!buf) return fail(XS_ERR_ARG, "null argument");
+        std::string names;
+        probe_kernel_names(names);
+        return copy_names(names.data(), names.size(), buf, cap);
     });
 }
 

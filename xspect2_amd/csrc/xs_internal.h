@@ -6,6 +6,7 @@
 #include <exception>
 #include <functional>
 #include <new>
+#include <string>
 #include <thread>
 #include <type_traits>
 #include <utility>
@@ -86,10 +87,16 @@ hipError_t launch_scatter_units(const uint64_t* nseg, const uint64_t* unit_ofs, 
 int probe_blocks(uint64_t D, int* waves_per_block, size_t* lds_bytes);
 int probe_grid_cobs(const CobsView& bv, uint32_t k);
 int probe_grid_bloom();
+// kernel (optional): receives the name of the instantiation launched, a string
+// literal of the family's table ("fast<21,7>", "vslice<31,3>", "wide<31,1,C4,G3>",
+// "slots<0,0,8,2>", "general"; "bloom<21,7>", "bloom<0,0>").
 hipError_t launch_probe_cobs(const ReadView& rv, const CobsView& bv, uint32_t* hits,
-                             uint64_t* partials, int blocks, hipStream_t s);
+                             uint64_t* partials, int blocks, hipStream_t s, const char** kernel = nullptr);
 hipError_t launch_probe_bloom(const ReadView& rv, const BloomView& bv, uint32_t* hits,
-                              uint64_t* partials, int blocks, hipStream_t s);
+                              uint64_t* partials, int blocks, hipStream_t s, const char** kernel = nullptr);
+// Every compiled direct COBS probe instantiation, one name per line (the
+// families' tables, in dispatch order).
+void probe_kernel_names(std::string& out);
 // Profiling of the partitioned probes: an event recorded on the launch stream
 // at each pass boundary, tagged with the pass that just ended (kPassStart opens
 // a query).  xs_bank_pass_stats sums the gaps per pass.

@@ -448,12 +448,20 @@ int probe_grid_cobs(const CobsView& bv, uint32_t k) {
 }
 
 hipError_t launch_probe_cobs(const ReadView& rv, const CobsView& bv, uint32_t* hits,
-                             uint64_t* partials, int blocks, hipStream_t s) {
-    if (cobs_fast(bv, rv.k)) return launch_cobs_fast(rv, bv, hits, partials, blocks, s);
-    if (vslice_take(bv)) return launch_cobs_vslice(rv, bv, hits, partials, blocks, s);
-    if (wide_for(bv)) return launch_cobs_wide(rv, bv, hits, partials, blocks, s);
-    if (slots_take(bv)) return launch_cobs_slots(rv, bv, hits, partials, blocks, s);
-    return launch_cobs_general(rv, bv, hits, partials, blocks, s);
+                             uint64_t* partials, int blocks, hipStream_t s, const char** kernel) {
+    if (cobs_fast(bv, rv.k)) return launch_cobs_fast(rv, bv, hits, partials, blocks, s, kernel);
+    if (vslice_take(bv)) return launch_cobs_vslice(rv, bv, hits, partials, blocks, s, kernel);
+    if (wide_for(bv)) return launch_cobs_wide(rv, bv, hits, partials, blocks, s, kernel);
+    if (slots_take(bv)) return launch_cobs_slots(rv, bv, hits, partials, blocks, s, kernel);
+    return launch_cobs_general(rv, bv, hits, partials, blocks, s, kernel);
+}
+
+void probe_kernel_names(std::string& out) {
+    fast_kernel_names(out);
+    vslice_kernel_names(out);
+    wide_kernel_names(out);
+    slots_kernel_names(out);
+    out += "general\n";
 }
 
 int probe_grid_bloom() {
@@ -462,11 +470,13 @@ int probe_grid_bloom() {
 }
 
 hipError_t launch_probe_bloom(const ReadView& rv, const BloomView& bv, uint32_t* hits,
-                              uint64_t* partials, int blocks, hipStream_t s) {
-    if (rv.k == 21 && bv.K == 7)
-        probe_bloom_kernel<21, 7, kBloomSplit><<<blocks, kProbeThreads, 0, s>>>(rv, bv, hits, partials);
-    else
-        probe_bloom_kernel<0, 0, kBloomSplit><<<blocks, kProbeThreads, 0, s>>>(rv, bv, hits, partials);
+                              uint64_t* partials, int blocks, hipStream_t s, const char** kernel) {
+    using BloomFn = void (*)(ReadView, BloomView, uint32_t*, uint64_t*);
+    static const struct { const char* name; BloomFn fn; } kBloomKernels[2] = {
+        {"bloom<21,7>", probe_bloom_kernel<21, 7, kBloomSplit>}, {"bloom<0,0>", probe_bloom_kernel<0, 0, kBloomSplit>}};
+    const auto& e = kBloomKernels[rv.k == 21 && bv.K == 7 ? 0 : 1];
+    if (kernel) *kernel = e.name;
+    e.fn<<<blocks, kProbeThreads, 0, s>>>(rv, bv, hits, partials);
     return hipGetLastError();
 }
 

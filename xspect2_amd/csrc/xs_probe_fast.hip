@@ -110,29 +110,33 @@ bool cobs_fast(const CobsView& bv, uint32_t k) {
            ((k == 21 && bv.h == 7) || (k == 31 && bv.h == 1));
 }
 
-template <int KT, int HT>
-static hipError_t launch_fast_t(const ReadView& rv, const FastBank& fb, uint32_t* hits,
-                                uint64_t* partials, int blocks, hipStream_t s) {
-    probe_cobs_fast<KT, HT><<<blocks, kProbeThreads, 0, s>>>(rv, fb, hits, partials);
-    return hipGetLastError();
-}
+using FastFn = void (*)(ReadView, FastBank, uint32_t*, uint64_t*);
+
+// Every compiled instantiation: name and kernel from one entry.
+static const ProbeKernel<FastFn> kFastKernels[2] = {{"fast<21,7>", probe_cobs_fast<21, 7>},
+                                                    {"fast<31,1>", probe_cobs_fast<31, 1>}};
+
+static const ProbeKernel<FastFn>& pick_fast(uint32_t k) { return kFastKernels[k == 21 ? 0 : 1]; }
+
+void fast_kernel_names(std::string& out) { table_names(kFastKernels, out); }
 
 int grid_cobs_fast(uint32_t k) {
-    static std::atomic<int> g21{0}, g31{0};
-    if (k == 21) return cached_grid(g21, [] { return resident_grid(probe_cobs_fast<21, 7>, kProbeThreads, 0); });
-    return cached_grid(g31, [] { return resident_grid(probe_cobs_fast<31, 1>, kProbeThreads, 0); });
+    static std::atomic<int> grid[2];
+    return cached_grid(grid[k == 21 ? 0 : 1], [&] { return resident_grid(pick_fast(k).fn, kProbeThreads, 0); });
 }
 
 hipError_t launch_cobs_fast(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                            int blocks, hipStream_t s) {
+                            int blocks, hipStream_t s, const char** kernel) {
     FastBank fb;
     fb.rows = bv.rows;
     fb.sig = bv.sig0;
     fb.magic = barrett_magic(bv.sig0);
     fb.D = (uint32_t)bv.D;
     fb.nwords = (uint32_t)((bv.D + 31) / 32);
-    if (rv.k == 21) return launch_fast_t<21, 7>(rv, fb, hits, partials, blocks, s);
-    return launch_fast_t<31, 1>(rv, fb, hits, partials, blocks, s);
+    const ProbeKernel<FastFn>& e = pick_fast(rv.k);
+    if (kernel) *kernel = e.name;
+    e.fn<<<blocks, kProbeThreads, 0, s>>>(rv, fb, hits, partials);
+    return hipGetLastError();
 }
 
 }  // namespace xs

@@ -145,10 +145,11 @@ int grid_cobs_general(const CobsView& bv) {
 }
 
 hipError_t launch_cobs_general(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                               int blocks, hipStream_t s) {
+                               int blocks, hipStream_t s, const char** kernel) {
     int wpb;
     size_t lds;
     if (probe_blocks(bv.D, &wpb, &lds) != 0) return hipErrorInvalidValue;
+    if (kernel) *kernel = "general";  // one name for its three (k, h) variants
     const uint32_t dpad = (uint32_t)((bv.D + 127) / 128 * 128);
     if (rv.k == 21 && bv.h == 7) return launch_cobs_t<21, 7>(rv, bv, hits, partials, blocks, wpb, lds, dpad, s);
     if (rv.k == 31 && bv.h == 1) return launch_cobs_t<31, 1>(rv, bv, hits, partials, blocks, wpb, lds, dpad, s);

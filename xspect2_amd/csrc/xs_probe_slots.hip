@@ -178,53 +178,61 @@ static SlotShape slots_for(const CobsView& bv) {
 
 using SlotsFn = void (*)(ReadView, CobsView, uint32_t*, uint64_t*, uint32_t);
 
-template <int KT, int HT>
-static SlotsFn slots_fn_classic(SlotShape s) {
-    return s.cm == 4 ? probe_cobs_slots<KT, HT, 1, 4> : probe_cobs_slots<KT, HT, 1, 8>;
+// The shapes slots_for returns, in table order.
+constexpr int kSlotShapes = 10;
+static const SlotShape kShapes[kSlotShapes] = {{1, 4}, {1, 8}, {4, 1}, {8, 1}, {16, 1}, {4, 2}, {8, 2}, {2, 4}, {3, 4}, {4, 4}};
+
+static int shape_index(SlotShape s) {  // 0..kSlotShapes - 1 (kSlotShapes: not a slot shape)
+    for (int i = 0; i < kSlotShapes; ++i)
+        if (kShapes[i].gm == s.gm && kShapes[i].cm == s.cm) return i;
+    return kSlotShapes;
 }
 
-template <int KT, int HT>
-static SlotsFn slots_fn(SlotShape s) {
-    if (s.gm == 1) return slots_fn_classic<KT, HT>(s);
-    if (s.cm == 1) return s.gm == 4 ? probe_cobs_slots<KT, HT, 4, 1> : s.gm == 8 ? probe_cobs_slots<KT, HT, 8, 1>
-                                                                                  : probe_cobs_slots<KT, HT, 16, 1>;
-    if (s.cm == 2) return s.gm == 4 ? probe_cobs_slots<KT, HT, 4, 2> : probe_cobs_slots<KT, HT, 8, 2>;
-    return s.gm == 2 ? probe_cobs_slots<KT, HT, 2, 4> : s.gm == 3 ? probe_cobs_slots<KT, HT, 3, 4>
-                                                                  : probe_cobs_slots<KT, HT, 4, 4>;
+// Every compiled instantiation, [(k, h) variant][shape_index]: name and kernel
+// from one entry.  Species banks are classic, so (21, 7) is compiled for the
+// one-group shapes only.
+#define XS_SLOTS(KT, HT, GM, CM) {"slots<" #KT "," #HT "," #GM "," #CM ">", probe_cobs_slots<KT, HT, GM, CM>}
+#define XS_SLOTS_NONE {nullptr, nullptr}
+#define XS_SLOTS_SHAPES(KT, HT)                                                                       \
+    XS_SLOTS(KT, HT, 1, 4), XS_SLOTS(KT, HT, 1, 8), XS_SLOTS(KT, HT, 4, 1), XS_SLOTS(KT, HT, 8, 1),  \
+    XS_SLOTS(KT, HT, 16, 1), XS_SLOTS(KT, HT, 4, 2), XS_SLOTS(KT, HT, 8, 2), XS_SLOTS(KT, HT, 2, 4), \
+    XS_SLOTS(KT, HT, 3, 4), XS_SLOTS(KT, HT, 4, 4)
+static const ProbeKernel<SlotsFn> kSlotsKernels[3 * kSlotShapes] = {
+    XS_SLOTS(21, 7, 1, 4), XS_SLOTS(21, 7, 1, 8), XS_SLOTS_NONE, XS_SLOTS_NONE, XS_SLOTS_NONE,
+    XS_SLOTS_NONE, XS_SLOTS_NONE, XS_SLOTS_NONE, XS_SLOTS_NONE, XS_SLOTS_NONE,
+    XS_SLOTS_SHAPES(31, 1),
+    XS_SLOTS_SHAPES(0, 0)};
+#undef XS_SLOTS_SHAPES
+#undef XS_SLOTS_NONE
+#undef XS_SLOTS
+
+// s = slots_for(bv), a slot shape
+static const ProbeKernel<SlotsFn>& pick_slots(uint32_t k, uint32_t h, SlotShape s) {
+    int v = kh_variant(k, h);
+    if (v == 0 && s.gm > 1) v = 2;  // species (k, h) on a compact bank: the general-(k, h) kernel
+    return kSlotsKernels[v * kSlotShapes + shape_index(s)];
 }
 
-static SlotsFn pick_slots(uint32_t k, uint32_t h, SlotShape s) {
-    switch (kh_variant(k, h)) {
-        case 0: return s.gm == 1 ? slots_fn_classic<21, 7>(s) : slots_fn<0, 0>(s);  // species banks are classic
-        case 1: return slots_fn<31, 1>(s);
-        default: return slots_fn<0, 0>(s);
-    }
-}
-
-static int shape_index(SlotShape s) {  // 0..12, for the grid cache
-    static const int gms[13] = {1, 1, 0, 0, 4, 8, 16, 4, 8, 2, 3, 4, 0};
-    static const int cms[13] = {4, 8, 0, 0, 1, 1, 1, 2, 2, 4, 4, 4, 0};
-    for (int i = 0; i < 12; ++i)
-        if (gms[i] == s.gm && cms[i] == s.cm) return i;
-    return 12;
-}
-
+void slots_kernel_names(std::string& out) { table_names(kSlotsKernels, out); }
 
 bool slots_take(const CobsView& bv) { return slots_for(bv).gm != 0; }
 
 int grid_cobs_slots(const CobsView& bv, uint32_t k) {
-    static std::atomic<int> slots[3][13];
+    static std::atomic<int> slots[3][kSlotShapes];
     const SlotShape sh = slots_for(bv);
     // LDS is 16 KB at most: residency is set by registers, not by D
     return cached_grid(slots[kh_variant(k, bv.h)][shape_index(sh)],
-                       [&] { return resident_grid(pick_slots(k, bv.h, sh), kProbeThreads, 16384); });
+                       [&] { return resident_grid(pick_slots(k, bv.h, sh).fn, kProbeThreads, 16384); });
 }
 
 hipError_t launch_cobs_slots(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                             int blocks, hipStream_t s) {
+                             int blocks, hipStream_t s, const char** kernel) {
     const size_t lds = slots_lds(bv);
-    pick_slots(rv.k, bv.h, slots_for(bv))<<<blocks, kProbeThreads, lds, s>>>(rv, bv, hits, partials,
-                                                                           (uint32_t)(lds / sizeof(uint64_t)));
+    const SlotShape sh = slots_for(bv);
+    if (sh.gm == 0) return hipErrorInvalidValue;  // not a slot shape (slots_take is false)
+    const ProbeKernel<SlotsFn>& e = pick_slots(rv.k, bv.h, sh);
+    if (kernel) *kernel = e.name;
+    e.fn<<<blocks, kProbeThreads, lds, s>>>(rv, bv, hits, partials, (uint32_t)(lds / sizeof(uint64_t)));
     return hipGetLastError();
 }
 

@@ -230,7 +230,10 @@ __global__ void __launch_bounds__(kProbeThreads, kVsMinBlocks) probe_cobs_vslice
 
 // ------------------------------------------------------------------ launch
 // Banks of 1-4 groups of 64-byte pages (512 docs each) with one hash, whose
-// image fits 32-bit offsets: XspecT's MLST loci of up to 2048 alleles.
+// image fits 32-bit offsets: XspecT's MLST loci of up to 2048 alleles.  The
+// bank kind is not asked: a classic bank (or doc slice) of 505-512 docs with
+// one hash has a 64-byte page too and is taken
+// (tests/test_gpu_probe_kernels.py pins both).
 bool vslice_take(const CobsView& bv) {
     return bv.G >= 1 && bv.G <= 4 && bv.h == 1 && bv.page == 64 && bv.pitch == 64 && bv.D <= bv.G * 512ull &&
            bv.sig_max < (1ull << 30) && (uint64_t)bv.G * bv.sig_max * 64 < (1ull << 32);
@@ -238,23 +241,30 @@ bool vslice_take(const CobsView& bv) {
 
 using VsFn = void (*)(ReadView, CobsView, uint32_t*, uint64_t*);
 
-template <int KT>
-static VsFn pick_vslice_g(uint32_t G) {
-    return G == 1 ? probe_cobs_vslice<KT, 1> : G == 2 ? probe_cobs_vslice<KT, 2>
-         : G == 3 ? probe_cobs_vslice<KT, 3> : probe_cobs_vslice<KT, 4>;
+// Every compiled instantiation, [k == 31 ? 0 : 1][G - 1]: name and kernel from one entry.
+#define XS_VSLICE(KT, GM) {"vslice<" #KT "," #GM ">", probe_cobs_vslice<KT, GM>}
+static const ProbeKernel<VsFn> kVsliceKernels[2 * 4] = {
+    XS_VSLICE(31, 1), XS_VSLICE(31, 2), XS_VSLICE(31, 3), XS_VSLICE(31, 4),
+    XS_VSLICE(0, 1),  XS_VSLICE(0, 2),  XS_VSLICE(0, 3),  XS_VSLICE(0, 4)};
+#undef XS_VSLICE
+
+static const ProbeKernel<VsFn>& pick_vslice(uint32_t k, uint32_t G) {
+    return kVsliceKernels[(k == 31 ? 0 : 4) + (G - 1)];  // G = 1..4 (vslice_take)
 }
 
-static VsFn pick_vslice(uint32_t k, uint32_t G) { return k == 31 ? pick_vslice_g<31>(G) : pick_vslice_g<0>(G); }
+void vslice_kernel_names(std::string& out) { table_names(kVsliceKernels, out); }
 
 int grid_cobs_vslice(const CobsView& bv, uint32_t k) {
     static std::atomic<int> grid[2][4];  // k == 31 x G
     return cached_grid(grid[k == 31 ? 0 : 1][bv.G - 1],
-                       [&] { return resident_grid(pick_vslice(k, bv.G), kProbeThreads, 0); });
+                       [&] { return resident_grid(pick_vslice(k, bv.G).fn, kProbeThreads, 0); });
 }
 
 hipError_t launch_cobs_vslice(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                              int blocks, hipStream_t s) {
-    pick_vslice(rv.k, bv.G)<<<blocks, kProbeThreads, 0, s>>>(rv, bv, hits, partials);
+                              int blocks, hipStream_t s, const char** kernel) {
+    const ProbeKernel<VsFn>& e = pick_vslice(rv.k, bv.G);
+    if (kernel) *kernel = e.name;
+    e.fn<<<blocks, kProbeThreads, 0, s>>>(rv, bv, hits, partials);
     return hipGetLastError();
 }
 

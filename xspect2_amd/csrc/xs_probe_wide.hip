@@ -208,43 +208,53 @@ using WideFn = void (*)(ReadView, CobsView, uint32_t*, uint64_t*, uint32_t);
 // MLST loci (3 groups: 5.67 / 5.42 / 6.29 ms for 1 / 2 / 4; r01_wide_compact.txt).
 constexpr int kWideInFlight = 2;
 
-template <int KT, int HT, int GM>
-static WideFn wide_fn_groups(int c) {
-    constexpr int P = kWideInFlight;
-    return c == 2 ? probe_cobs_wide<KT, HT, 2, P, GM> : probe_cobs_wide<KT, HT, 4, P, GM>;
+// Every compiled instantiation, [(k, h) variant][G - 1][C = 2, 4, 8, 16]: name
+// and kernel from one entry.  One group takes every C, 2..4 groups C = 2 and 4
+// (wide_for); species banks are classic, so (21, 7) is compiled for one group only.
+#define XS_WIDE(KT, HT, C, GM) {"wide<" #KT "," #HT ",C" #C ",G" #GM ">", probe_cobs_wide<KT, HT, C, kWideInFlight, GM>}
+#define XS_WIDE_NONE {nullptr, nullptr}
+#define XS_WIDE_GROUPS(KT, HT)                                                                  \
+    XS_WIDE(KT, HT, 2, 1), XS_WIDE(KT, HT, 4, 1), XS_WIDE(KT, HT, 8, 1), XS_WIDE(KT, HT, 16, 1), \
+    XS_WIDE(KT, HT, 2, 2), XS_WIDE(KT, HT, 4, 2), XS_WIDE_NONE, XS_WIDE_NONE,                   \
+    XS_WIDE(KT, HT, 2, 3), XS_WIDE(KT, HT, 4, 3), XS_WIDE_NONE, XS_WIDE_NONE,                   \
+    XS_WIDE(KT, HT, 2, 4), XS_WIDE(KT, HT, 4, 4), XS_WIDE_NONE, XS_WIDE_NONE
+static const ProbeKernel<WideFn> kWideKernels[3 * 4 * 4] = {
+    XS_WIDE(21, 7, 2, 1), XS_WIDE(21, 7, 4, 1), XS_WIDE(21, 7, 8, 1), XS_WIDE(21, 7, 16, 1),
+    XS_WIDE_NONE, XS_WIDE_NONE, XS_WIDE_NONE, XS_WIDE_NONE,
+    XS_WIDE_NONE, XS_WIDE_NONE, XS_WIDE_NONE, XS_WIDE_NONE,
+    XS_WIDE_NONE, XS_WIDE_NONE, XS_WIDE_NONE, XS_WIDE_NONE,
+    XS_WIDE_GROUPS(31, 1),
+    XS_WIDE_GROUPS(0, 0)};
+#undef XS_WIDE_GROUPS
+#undef XS_WIDE_NONE
+#undef XS_WIDE
+
+static int wide_c_index(int c) { return c == 2 ? 0 : c == 4 ? 1 : c == 8 ? 2 : 3; }
+
+// c = wide_for(bv) (non-zero), G = 1..4
+static const ProbeKernel<WideFn>& pick_wide(uint32_t k, uint32_t h, int c, uint32_t G) {
+    int v = kh_variant(k, h);
+    if (v == 0 && G > 1) v = 2;  // species (k, h) on a compact bank: the general-(k, h) kernel
+    return kWideKernels[(v * 4 + (int)(G - 1)) * 4 + wide_c_index(c)];
 }
 
-template <int KT, int HT>
-static WideFn wide_fn(int c, uint32_t G) {
-    constexpr int P = kWideInFlight;
-    if (G == 2) return wide_fn_groups<KT, HT, 2>(c);
-    if (G == 3) return wide_fn_groups<KT, HT, 3>(c);
-    if (G == 4) return wide_fn_groups<KT, HT, 4>(c);
-    return c == 2 ? probe_cobs_wide<KT, HT, 2, P, 1> : c == 4 ? probe_cobs_wide<KT, HT, 4, P, 1>
-         : c == 8 ? probe_cobs_wide<KT, HT, 8, P, 1> : probe_cobs_wide<KT, HT, 16, P, 1>;
-}
-
-static WideFn pick_wide(uint32_t k, uint32_t h, int c, uint32_t G) {
-    switch (kh_variant(k, h)) {
-        case 0: return G == 1 ? wide_fn<21, 7>(c, 1) : wide_fn<0, 0>(c, G);  // species banks are classic
-        case 1: return wide_fn<31, 1>(c, G);
-        default: return wide_fn<0, 0>(c, G);
-    }
-}
+void wide_kernel_names(std::string& out) { table_names(kWideKernels, out); }
 
 int grid_cobs_wide(const CobsView& bv, uint32_t k) {
     static std::atomic<int> wide[3][4][4];  // (k, h) variant x G x C
     const int c = wide_for(bv);
-    return cached_grid(wide[kh_variant(k, bv.h)][bv.G - 1][c == 2 ? 0 : c == 4 ? 1 : c == 8 ? 2 : 3], [&] {
-        return resident_grid(pick_wide(k, bv.h, c, bv.G), kProbeThreads, slots_lds(bv) > 8192 ? 16384 : 8192);
+    return cached_grid(wide[kh_variant(k, bv.h)][bv.G - 1][wide_c_index(c)], [&] {
+        return resident_grid(pick_wide(k, bv.h, c, bv.G).fn, kProbeThreads, slots_lds(bv) > 8192 ? 16384 : 8192);
     });
 }
 
 hipError_t launch_cobs_wide(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                            int blocks, hipStream_t s) {
+                            int blocks, hipStream_t s, const char** kernel) {
     const size_t lds = slots_lds(bv);
-    pick_wide(rv.k, bv.h, wide_for(bv), bv.G)<<<blocks, kProbeThreads, lds, s>>>(
-        rv, bv, hits, partials, (uint32_t)(lds / sizeof(uint64_t)));
+    const ProbeKernel<WideFn>& e = pick_wide(rv.k, bv.h, wide_for(bv), bv.G);
+    if (!e.fn) return hipErrorInvalidDeviceFunction;  // a table slot wide_for never selects
+    if (kernel) *kernel = e.name;
+    e.fn<<<blocks, kProbeThreads, lds, s>>>(rv, bv, hits, partials, (uint32_t)(lds / sizeof(uint64_t)));
     return hipGetLastError();
 }
 
