@@ -1,7 +1,7 @@
 """Hit matrices back to host memory (xs_query / xs_query_hits, GPU).
 
 The rows of every chunk of a host call go back on a worker thread while the
-next chunks are probed (HitSink, xs_api.cpp): narrowed on the device to the
+next chunks are probed (HitSink, xs_hitsink.h): narrowed on the device to the
 narrowest width that holds the batch's largest k-mer count, staged through a
 ring of three 32 MiB pinned slots and widened on the host into the caller's
 array; a pinned destination takes the rows by DMA in its own width.  Every

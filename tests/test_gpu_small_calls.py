@@ -1,4 +1,4 @@
-"""Small host calls (query_small in xs_api.cpp): a request of up to 4096 reads
+"""Small host calls (query_small in xs_query.cpp): a request of up to 4096 reads
 and 1 MiB of sequence travels in one pinned buffer (host-built unit map, one
 H2D copy, the direct probe kernel, one D2H copy, one sync) instead of
 query_host's unit pipeline and staging ring (GPU).

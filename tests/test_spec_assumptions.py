@@ -101,7 +101,7 @@ def test_b4_rbloom_sizing(oracle_mod):
 
 def test_c_file_layouts(oracle_mod):
     """A6 / B5: the spec writers produce the layouts the library reads
-    (xs_api.cpp read_cobs_header, xs_bank_open): header sizes for a 3-doc
+    (xs_bank_io.cpp read_cobs_header, xs_bank_open): header sizes for a 3-doc
     classic index, a compact index padded to its page, an rbloom file."""
     rows = np.arange(5 * 1, dtype=np.uint8)
     f = oracle_mod.cobs_classic_file(["a", "bb", "c"], K, 7, 5, rows)
