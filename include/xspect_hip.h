@@ -238,6 +238,42 @@ int xs_mlst_query(xs_bank* bank, const char* seqs, const uint64_t* offsets, uint
                   uint32_t* direct_hits, uint64_t* owner_scores, uint32_t* owner_first,
                   uint32_t* owner_first_score);
 
+/* ---- MLST typing: the top allele per record and locus, reduced on the device.
+ * The reference keeps only the first item of each locus' COBS result per record
+ * (probabilistic_filter_mlst_model.py:272-286: score descending, ties by doc
+ * index) and the sufficiency test over those scores (:288-303, :428-449).  For
+ * a hit row of num_docs counts:
+ *   top = the lowest doc holding the row's maximum, top_score = that maximum,
+ *   n_tied = the docs holding it (not in the reference: how ambiguous the call is).
+ * An all-zero row gives top 0, top_score 0, n_tied num_docs. */
+#define XS_MLST_NONE 0xFFFFFFFFu /* no allele (used by the Python layer for "N/A") */
+
+/* The reduction alone, over a device matrix (n x num_docs uint32, row-major),
+ * asynchronous on `stream`.  Row r's values are written at index r * out_stride
+ * of d_top, d_top_score and d_n_tied (may be NULL), so one call per locus fills
+ * one column of n x n_loci arrays (out_stride = n_loci, pointers offset by the
+ * locus). */
+int xs_mlst_top_device(const uint32_t* d_hits, uint64_t n, uint64_t num_docs, uint32_t* d_top,
+                       uint32_t* d_top_score, uint32_t* d_n_tied, uint64_t out_stride, void* stream);
+
+/* Every locus of a scheme for n host reads in one call (replaces the per-locus,
+ * per-record index.search loop of probabilistic_filter_mlst_model.py:272-286):
+ * the reads are uploaded once, probed against each locus in chunks of R reads
+ * (R x the largest locus' docs x 4 bytes <= workspace_bytes, R >= 1; 0: 4 GiB)
+ * and each chunk's rows reduced on the device.  No hit matrix crosses to the
+ * host.  loci: n_loci distinct COBS banks on one device with one k.  top,
+ * top_score, n_tied (NULL ok): n x n_loci, row-major, host memory;
+ * num_kmers_out (NULL ok): n entries.  n = 0 writes nothing. */
+int xs_mlst_type(xs_bank* const* loci, uint32_t n_loci, const char* seqs, const uint64_t* offsets, uint64_t n,
+                 uint32_t step, uint64_t workspace_bytes, uint32_t* top, uint32_t* top_score, uint32_t* n_tied,
+                 uint64_t* num_kmers_out);
+
+/* The same for reads already in HBM (an xs_fastx_dbatch: d_seqs, seq_bytes,
+ * d_offsets with [0] = 0); outputs are host memory. */
+int xs_mlst_type_device(xs_bank* const* loci, uint32_t n_loci, const void* d_seqs, uint64_t seq_bytes,
+                        const uint64_t* d_offsets, uint64_t n, uint32_t step, uint64_t workspace_bytes,
+                        uint32_t* top, uint32_t* top_score, uint32_t* n_tied, uint64_t* num_kmers_out);
+
 /* Record HIP events around the probe kernel of every query on this handle. */
 int xs_bank_set_profiling(xs_bank* bank, int on);
 /* Duration of the probe kernel of the last profiled query, milliseconds. */

@@ -1,0 +1,228 @@
+"""MLST typing over reads at BASELINE config-4 size, the existing path and the
+new one in one run on one GPU:
+
+    python tools/mlst_typing_bench.py [--reads 1000000] [--out FILE] [--time-limit 900]
+
+Banks and reads follow tests/test_gpu_fullsize.py::test_config4_mlst_full_size:
+7 loci x 1430 alleles of 400-600 bp (COBS compact, k = 31, one hash, fpr 0.001,
+64-byte pages), error-free 150 bp windows of random alleles.  Three legs, each
+after its own warm-up, each repeat timed by a host clock around a call that ends
+synchronised:
+
+  a  7 x Bank.mlst_query on the packed host reads: the per-locus path of
+     ProbabilisticFilterMlstSchemeModel._locus_rows (reads uploaded per locus, the
+     n x D uint32 rows copied back per locus)
+  b  mlst_type on the same host reads (one upload, rows reduced on the device)
+  c  mlst_type on the reads already in HBM
+
+Beside them, for leg c's account: the device-resident probe step (7 x
+query_device into an n x D device matrix), the reduction alone over that matrix
+(7 x mlst_top_device between two device events), and leg c at other workspace
+sizes.  Before timing, legs b and c must agree, and equal numpy's argmax / max /
+count over leg a's rows on a sample of reads.  Prints one JSON line (and writes
+it to --out).  The run ends itself after --time-limit seconds.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import signal
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+K, LOCI, ALLELES, PAGE, READ_LEN = 31, 7, 1430, 64, 150
+
+
+def make_scheme(torch, dev, rng):
+    """The loci banks, built on the device, and their alleles padded to one array."""
+    from xspect2_amd.bank import Bank, cobs_signature_size
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    s = torch.cuda.current_stream(dev).cuda_stream
+    banks = []
+    padded = np.zeros((LOCI, ALLELES, 620), dtype=np.uint8)
+    sizes = np.zeros((LOCI, ALLELES), dtype=np.int64)
+    for li in range(LOCI):
+        base = acgt[rng.integers(0, 4, 620)]
+        alleles = []
+        for _ in range(ALLELES):
+            a = base[:int(rng.integers(400, 601))].copy()
+            pos = rng.integers(0, a.size, int(rng.integers(0, 12)))
+            a[pos] = acgt[(np.searchsorted(acgt, a[pos]) + 1) % 4]
+            alleles.append(a)
+        alleles.sort(key=lambda a: a.size)  # COBS compact: docs sorted by size
+        per = 8 * PAGE
+        sig = [cobs_signature_size(max(a.size for a in alleles[g:g + per]) - K + 1, 1, 0.001)
+               for g in range(0, ALLELES, per)]
+        bank = Bank.create_cobs(K, 1, sig, ALLELES, [f"Allele_ID_{i}" for i in range(ALLELES)], page_size=PAGE,
+                                compact=True, device=dev.index)
+        buf = np.concatenate(alleles)
+        offs = np.zeros(ALLELES + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([a.size for a in alleles])
+        bank.build_device(torch.from_numpy(buf).to(dev), buf.size, torch.from_numpy(offs).to(dev), ALLELES,
+                          torch.arange(ALLELES, dtype=torch.int32, device=dev), stream=s)
+        torch.cuda.synchronize(dev)
+        for i, a in enumerate(alleles):
+            padded[li, i, :a.size] = a
+            sizes[li, i] = a.size
+        banks.append(bank)
+    return banks, padded, sizes
+
+
+def make_reads(rng, padded, sizes, n):
+    li = rng.integers(0, LOCI, n)
+    ai = rng.integers(0, ALLELES, n)
+    st = (rng.random(n) * (sizes[li, ai] - READ_LEN + 1)).astype(np.int64)
+    return padded[li[:, None], ai[:, None], st[:, None] + np.arange(READ_LEN)[None, :]]
+
+
+def timed(fn, warmup, repeats, sync):
+    for _ in range(warmup):
+        fn()
+    sync()
+    ms = []
+    for _ in range(repeats):
+        t = time.perf_counter()
+        fn()
+        sync()
+        ms.append((time.perf_counter() - t) * 1e3)
+    return {"ms": [round(x, 3) for x in ms], "median_ms": round(statistics.median(ms), 3),
+            "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "warmup": warmup, "repeats": repeats}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=1_000_000)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--existing-warmup", type=int, default=1, help="leg a (seconds per call at full size)")
+    ap.add_argument("--existing-repeats", type=int, default=3)
+    ap.add_argument("--sweep-mib", type=int, nargs="*", default=[256, 1024, 16384],
+                    help="leg c again with these workspace sizes")
+    ap.add_argument("--time-limit", type=int, default=900, help="seconds after which the run ends itself")
+    ap.add_argument("--out", type=Path, default=None)
+    a = ap.parse_args()
+
+    def too_long(*_):
+        raise SystemExit(f"mlst_typing_bench: time limit of {a.time_limit} s reached")
+
+    signal.signal(signal.SIGALRM, too_long)
+    signal.alarm(a.time_limit)
+
+    import torch
+    from xspect2_amd import _lib
+    from xspect2_amd.bank import DeviceReads, mlst_top_device, mlst_type
+    from xspect2_amd.packing import pack_fixed
+
+    if not torch.cuda.is_available():
+        raise SystemExit("mlst_typing_bench: no GPU (nothing is measured without one)")
+    dev = torch.device("cuda", 0)
+    s = torch.cuda.current_stream(dev).cuda_stream
+
+    def sync():
+        torch.cuda.synchronize(dev)
+
+    rng = np.random.default_rng(4242)
+    n = a.reads
+    banks, padded, sizes = make_scheme(torch, dev, rng)
+    reads = make_reads(rng, padded, sizes, n)
+    packed = pack_fixed(reads)
+    d_seqs = torch.from_numpy(reads.reshape(-1)).to(dev)
+    d_offs = torch.arange(n + 1, dtype=torch.int64, device=dev) * READ_LEN
+    sync()
+    dreads = DeviceReads(d_seqs, n * READ_LEN, d_offs, n, READ_LEN)
+
+    # ---- results first: b == c, and both equal the reduction of leg a's rows on a sample
+    sample = np.unique(np.concatenate([np.arange(min(n, 500)), np.arange(max(0, n - 500), n),
+                                       rng.integers(0, n, 2000)]))
+    got_b = mlst_type(banks, packed)
+    got_c = mlst_type(banks, dreads)
+    same_bc = all(np.array_equal(x, y) for x, y in zip(got_b, got_c))
+    mismatches = 0
+    for l, bank in enumerate(banks):
+        rows = bank.mlst_query(packed, [], [], 0)[0][sample]
+        m = rows.max(axis=1)
+        mismatches += int((got_b[0][sample, l] != rows.argmax(axis=1)).sum() + (got_b[1][sample, l] != m).sum()
+                          + (got_b[2][sample, l] != (rows == m[:, None]).sum(axis=1)).sum())
+        del rows
+    own = (got_b[1].max(axis=1) == READ_LEN - K + 1)  # an error-free window scores all its k-mers somewhere
+    checks = {"b_equals_c": bool(same_bc), "sample_reads": int(sample.size), "sample_mismatches_vs_leg_a_rows": mismatches,
+              "reads_with_a_full_score": int(own.sum()), "num_kmers_ok": bool((got_b[3] == READ_LEN - K + 1).all())}
+    checks["ok"] = bool(same_bc and mismatches == 0 and own.all() and checks["num_kmers_ok"])
+
+    # ---- the legs
+    def leg_a():
+        for bank in banks:
+            bank.mlst_query(packed, [], [], 0)
+
+    legs = {
+        "a_mlst_query_per_locus": timed(leg_a, a.existing_warmup, a.existing_repeats, sync),
+        "b_mlst_type_host_reads": timed(lambda: mlst_type(banks, packed), a.warmup, a.repeats, sync),
+        "c_mlst_type_device_reads": timed(lambda: mlst_type(banks, dreads), a.warmup, a.repeats, sync),
+    }
+    sweep = {str(mib): timed(lambda mib=mib: mlst_type(banks, dreads, workspace_bytes=mib << 20), a.warmup,
+                             a.repeats, sync) for mib in a.sweep_mib}
+
+    # ---- leg c's parts: the probe step on device reads, and the reduction alone (device events)
+    hits = torch.empty((n, ALLELES), dtype=torch.int32, device=dev)
+    d_nk = torch.empty(n, dtype=torch.int64, device=dev)
+    tot = torch.empty(ALLELES + 1, dtype=torch.int64, device=dev)
+
+    def probe_step():
+        for bank in banks:
+            bank.query_device(d_seqs, n * READ_LEN, d_offs, n, 1, hits, d_nk, tot, stream=s)
+
+    probe = timed(probe_step, a.warmup, a.repeats, sync)
+    outs = [torch.empty(n * LOCI, dtype=torch.int32, device=dev) for _ in range(3)]  # n x LOCI, row-major
+
+    def reduce_all():
+        for l in range(LOCI):
+            mlst_top_device(hits, n, ALLELES, outs[0][l:], outs[1][l:], outs[2][l:], LOCI, stream=s)
+
+    for _ in range(a.warmup):
+        reduce_all()
+    sync()
+    ev_ms = []
+    for _ in range(a.repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        reduce_all()
+        e1.record()
+        sync()
+        ev_ms.append(e0.elapsed_time(e1))
+    reduce_ms = statistics.median(ev_ms)
+    matrix_gb = LOCI * n * ALLELES * 4 / 1e9
+
+    med = {k: v["median_ms"] for k, v in legs.items()}
+    line = {
+        "tool": "mlst_typing_bench", "build_id": _lib.build_id(), "device": torch.cuda.get_device_name(dev),
+        "config": {"reads": n, "read_len": READ_LEN, "loci": LOCI, "alleles_per_locus": ALLELES, "k": K,
+                   "page_size": PAGE, "step": 1, "default_workspace_mib": 4096},
+        "checks": checks, "legs": legs,
+        "b_over_a_speedup": round(med["a_mlst_query_per_locus"] / med["b_mlst_type_host_reads"], 2),
+        "device_probe_step": probe,
+        "reduction_alone": {"median_ms": round(reduce_ms, 3), "ms": [round(x, 3) for x in ev_ms],
+                            "matrix_gb_read": round(matrix_gb, 2), "gb_per_s": round(matrix_gb / reduce_ms * 1e3, 1),
+                            "clock": "device events around 7 x mlst_top_device over the n x D device matrix"},
+        "c_over_probe_step": round(med["c_mlst_type_device_reads"] / probe["median_ms"], 2),
+        "c_workspace_sweep_mib": sweep,
+        "clock": "host perf_counter around calls that return synchronised (legs), a device synchronise (probe step)",
+    }
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        a.out.parent.mkdir(parents=True, exist_ok=True)
+        a.out.write_text(text + "\n")
+    for bank in banks:
+        bank.close()
+    return 0 if checks["ok"] else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -30,6 +30,7 @@ XS_PATH_GATHER = 0
 XS_PATH_PARTITIONED = 1
 
 XS_BEST_AMBIGUOUS = 0xFFFFFFFF
+XS_MLST_NONE = 0xFFFFFFFF
 
 XS_FASTX_FASTA = 1
 XS_FASTX_FASTQ = 2
@@ -145,6 +146,9 @@ SIGNATURES = {
     "xs_best_device": (_int, [_vp, _u64, _u64, _vp, _vp, _vp]),
     "xs_mlst_sum": (_int, [_vp, _vp, _vp, _u64, _u64, _u32, _vp]),
     "xs_mlst_query": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "xs_mlst_top_device": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp]),
+    "xs_mlst_type": (_int, [_vp, _u32, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp]),
+    "xs_mlst_type_device": (_int, [_vp, _u32, _vp, _u64, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp]),
     "xs_bank_set_profiling": (_int, [_vp, _int]),
     "xs_bank_last_probe_ms": (_int, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "xs_bank_probe_stats": (_int, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double),

@@ -532,6 +532,61 @@ def best_device(hits, n: int, num_docs: int, best, best_hits=None, stream: int |
     check(load().xs_best_device(_dptr(hits), n, num_docs, _dptr(best), _dptr(best_hits), stream))
 
 
+def mlst_top_device(hits, n: int, num_docs: int, top, top_score, n_tied=None, out_stride: int = 1,
+                    stream: int | None = None) -> None:
+    """xs_mlst_top_device: per row of a device hit matrix (n x num_docs uint32) the
+    lowest doc holding the maximum, that maximum, and (n_tied, optional) how many
+    docs hold it, written at index r * out_stride of each output."""
+    check(load().xs_mlst_top_device(_dptr(hits), n, num_docs, _dptr(top), _dptr(top_score), _dptr(n_tied),
+                                    out_stride, stream))
+
+
+class DeviceReads:
+    """Packed reads already in HBM, as two device tensors (or raw pointers): the
+    bytes, and n + 1 uint64 offsets starting at 0.  Taken where a device-mode
+    reader batch is (``mlst_type``, ``Bank.query``); the caller keeps the
+    tensors complete (synchronised) and alive for the call."""
+
+    def __init__(self, seqs, seq_bytes: int, offsets, n: int, max_len: int = 0):
+        self._keep = (seqs, offsets)
+        self.seqs_ptr, self.offsets_ptr = _dptr(seqs) or 0, _dptr(offsets) or 0
+        self.seq_bytes, self.n, self.max_len = int(seq_bytes), int(n), int(max_len)
+
+    def check_valid(self) -> None:
+        pass
+
+
+def mlst_type(banks: Sequence[Bank], reads, step: int = 1, workspace_bytes: int = 0):
+    """xs_mlst_type: every locus bank of a scheme over the same reads in one call.
+    Returns (top, top_score, n_tied, num_kmers): [n, len(banks)] uint32 arrays of
+    the top allele's doc index (lowest doc holding the row's maximum), its score
+    and the number of docs sharing it, and [n] uint64 sampled k-mer counts.
+
+    reads: a PackedReads, an iterable of sequences, or reads in HBM (a device-mode
+    reader batch or a ``DeviceReads``).  The reads go to the device once; each
+    locus' hit rows are reduced there, in chunks of reads whose rows fit
+    workspace_bytes (0: the library's default), and never reach the host."""
+    banks = list(banks)
+    if step < 1:
+        raise ValueError("step must be >= 1")
+    dev = _device_batch(reads)
+    if dev:
+        reads.check_valid()
+    pr = reads if dev or isinstance(reads, PackedReads) else pack_sequences(reads)
+    n, L = pr.n, len(banks)
+    handles = (ctypes.c_void_p * max(L, 1))(*[b.handle.value for b in banks])
+    top, score, tied = (_HOST_POOL.empty((n, L), np.uint32) for _ in range(3))  # recycled pages, see _HostPool
+    nk = np.empty(n, dtype=np.uint64)
+    outs = (_ptr(top) or None, _ptr(score) or None, _ptr(tied) or None, _ptr(nk) or None)
+    if dev:
+        check(load().xs_mlst_type_device(handles, L, pr.seqs_ptr or None, pr.seq_bytes, pr.offsets_ptr or None, n,
+                                         step, workspace_bytes, *outs))
+    else:
+        check(load().xs_mlst_type(handles, L, _ptr(pr.buf) or None, _ptr(pr.offsets), n, step, workspace_bytes,
+                                  *outs))
+    return top, score, tied, nk
+
+
 def gather_reads_device(seqs, offsets, index, m: int, out_seqs, out_offsets, stream: int | None = None) -> None:
     """xs_gather_reads_device: out read j = read index[j] at out_offsets[j]."""
     check(load().xs_gather_reads_device(_dptr(seqs), _dptr(offsets), _dptr(index), m, _dptr(out_seqs),
@@ -555,4 +610,4 @@ def _dptr(x) -> int | None:
 
 
 __all__ = ["Bank", "bloom_parameters", "cobs_signature_size", "KIND_NAMES", "pinned_empty", "max_kmers", "probe_kernel_names",
-           "XS_BANK_COBS_CLASSIC", "XS_BANK_COBS_COMPACT", "XS_BANK_RBLOOM", "_lib"]
+           "mlst_top_device", "mlst_type", "DeviceReads", "XS_BANK_COBS_CLASSIC", "XS_BANK_COBS_COMPACT", "XS_BANK_RBLOOM", "_lib"]

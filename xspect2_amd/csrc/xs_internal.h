@@ -234,6 +234,12 @@ constexpr uint32_t kBestAmbiguous = 0xFFFFFFFFu;
 hipError_t launch_best_doc(const uint32_t* hits, uint64_t n, uint64_t D, uint32_t* best,
                            uint32_t* best_hits, hipStream_t s);
 
+// Per row of an n x D matrix (xs_mlst_top.hip): top = the lowest doc holding the row's maximum,
+// top_score = that maximum, n_tied (may be null) = the docs holding it; row r's values go to
+// out[r * out_stride], so one launch fills one column of an n x loci array.
+hipError_t launch_mlst_top(const uint32_t* hits, uint64_t n, uint64_t D, uint32_t* top, uint32_t* top_score,
+                           uint32_t* n_tied, uint64_t out_stride, hipStream_t s);
+
 // dst[i] = src[i] as uint8 (hit_bytes 1) or uint16 (2); the caller guarantees the values fit.
 hipError_t launch_narrow_hits(const uint32_t* src, void* dst, uint64_t n, int hit_bytes, hipStream_t s,
                               uint32_t* overflow = nullptr);

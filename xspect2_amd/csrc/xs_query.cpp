@@ -612,6 +612,174 @@ int query_impl(xs_bank* b, const char* seqs, const uint64_t* offsets, uint64_t n
     return XS_OK;
 }
 
+// ---- MLST typing: every locus of a scheme, rows reduced on the device -----------
+// The reads are in HBM once (uploaded into the first locus' buffers, or a device reader's batch).
+// They are probed in chunks of R reads, R x Dmax x 4 <= the workspace: per chunk and locus the
+// probe fills the rows buffer and mlst_top_kernel reduces it into column l of the n x loci device
+// outputs, so the rows buffer does not grow with n and no hit matrix crosses PCIe.  Everything
+// runs on the first locus' stream; its buffers hold the reads, the rows and the outputs.
+constexpr uint64_t kMlstTypeWs = 4ull << 30;  // default cap of the rows buffer
+
+struct MlstTypeOut {
+    uint32_t *top, *top_score, *n_tied;  // n x loci each, host (n_tied may be null)
+    uint64_t* num_kmers;                 // n, host (may be null)
+};
+
+// The argument errors of xs_mlst_type / xs_mlst_type_device that need no device.
+int mlst_type_check(xs_bank* const* loci, uint32_t n_loci, uint64_t n, uint32_t step, const MlstTypeOut& out) {
+    if (!loci || (n && (!out.top || !out.top_score))) return fail(XS_ERR_ARG, "null argument");
+    if (n_loci == 0) return fail(XS_ERR_ARG, "n_loci must be >= 1");
+    if (step == 0) return fail(XS_ERR_ARG, "step must be >= 1");
+    for (uint32_t l = 0; l < n_loci; ++l) {
+        if (!loci[l]) return fail(XS_ERR_ARG, "null argument");
+        for (uint32_t j = 0; j < l; ++j)
+            if (loci[j] == loci[l]) return fail(XS_ERR_ARG, "locus %u is the same handle as locus %u", l, j);
+    }
+    for (uint32_t l = 0; l < n_loci; ++l) {
+        if (loci[l]->kind == XS_BANK_RBLOOM) return fail(XS_ERR_ARG, "MLST queries need a COBS bank (locus %u)", l);
+        if (loci[l]->device != loci[0]->device) return fail(XS_ERR_ARG, "locus %u is on another device than locus 0", l);
+        if (loci[l]->k != loci[0]->k) return fail(XS_ERR_ARG, "locus %u has another k than locus 0", l);
+    }
+    return XS_OK;
+}
+
+// Every locus' mutex, taken in address order: two calls over the same handles in any order cannot deadlock.
+struct LociLock {
+    std::vector<std::unique_lock<std::mutex>> held;
+    LociLock(xs_bank* const* loci, uint32_t n_loci) {
+        std::vector<xs_bank*> order(loci, loci + n_loci);
+        std::sort(order.begin(), order.end(), std::less<xs_bank*>());
+        for (xs_bank* b : order) held.emplace_back(b->mu);
+    }
+};
+
+// Host reads into b's device buffers on stream s (offsets rebased to 0, kept in b->offs_h for the
+// call): pageable bytes go through the pinned H2D ring, the copy of slot i behind the host's fill of
+// slot i+1.  The caller synchronises s before the source memory may change.
+int upload_reads(xs_bank* b, const char* seqs, const uint64_t* offsets, uint64_t n, hipStream_t s, Inputs* in) {
+    if (int rc = b->offs_h.ensure((n + 1) * 8)) return rc;
+    uint64_t* rb = static_cast<uint64_t*>(b->offs_h.p);
+    if (!rebase_offsets(offsets, n, rb)) return bad_offsets();
+    const uint64_t bytes = rb[n];
+    if (int rc = b->seqs.ensure(bytes + kPad)) return rc;
+    if (int rc = b->offs.ensure((n + 1) * 8)) return rc;
+    HIPCHK(hipMemcpyAsync(b->offs.p, rb, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    const char* src = seqs + offsets[0];
+    if (bytes && (bytes <= kHostFirst || is_pinned_host(src))) {
+        HIPCHK(hipMemcpyAsync(b->seqs.p, src, bytes, hipMemcpyHostToDevice, s));
+    } else if (bytes) {
+        for (int i = 0; i < 2; ++i) {
+            if (int rc = b->hstage[i].ensure(kHostChunk)) return rc;
+            if (!b->hstage_ev[i]) HIPCHK(hipEventCreateWithFlags(&b->hstage_ev[i], hipEventDisableTiming));
+        }
+        const int threads = host_threads();
+        uint64_t i = 0;
+        for (uint64_t off = 0; off < bytes; off += kHostChunk, ++i) {
+            const int slot = (int)(i & 1);
+            const size_t nb = (size_t)std::min<uint64_t>(kHostChunk, bytes - off);
+            if (i >= 2) HIPCHK(hipEventSynchronize(b->hstage_ev[slot]));  // the slot's last H2D is done
+            par_memcpy(b->hstage[slot].p, src + off, nb, threads);
+            HIPCHK(hipMemcpyAsync(b->seqs.as<uint8_t>() + off, b->hstage[slot].p, nb, hipMemcpyHostToDevice, s));
+            HIPCHK(hipEventRecord(b->hstage_ev[slot], s));
+        }
+    }
+    *in = Inputs{b->seqs.as<uint8_t>(), bytes, b->offs.as<uint64_t>(), n};
+    return XS_OK;
+}
+
+// Several device regions -> host memory, ordered after the work already on `st`; returns once
+// they are there.  d2h_pageable's ring over all the parts: a part of kD2hRingMin bytes or more
+// bound for pageable memory crosses in 32 MiB pieces through the two pinned slots, the DMA of one
+// piece behind the host threads' copy of the one before; the others are plain copies.
+struct D2hPart {
+    void* host;
+    const void* dev;
+    size_t bytes;
+};
+constexpr size_t kD2hRingMin = 1u << 20;
+int d2h_parts(xs_bank* b, const D2hPart* parts, int n_parts, hipStream_t st) {
+    constexpr size_t kChunk = 32u << 20;
+    const int threads = host_threads();
+    char* prev_host = nullptr;
+    size_t prev_n = 0, i = 0;
+    int prev_slot = -1;
+    for (int p = 0; p < n_parts; ++p) {
+        const D2hPart& part = parts[p];
+        if (!part.bytes) continue;
+        if (part.bytes < kD2hRingMin || is_pinned_host(part.host)) {
+            HIPCHK(hipMemcpyAsync(part.host, part.dev, part.bytes, hipMemcpyDeviceToHost, st));
+            continue;
+        }
+        for (size_t off = 0; off < part.bytes; off += kChunk, ++i) {
+            const int slot = (int)(i & 1);  // free: its piece i - 2 was copied out while piece i - 1 crossed
+            const size_t nb = std::min(kChunk, part.bytes - off);
+            if (int rc = b->stage[slot].ensure(kChunk)) return rc;
+            if (!b->stage_ev[slot]) HIPCHK(hipEventCreateWithFlags(&b->stage_ev[slot], hipEventDisableTiming));
+            HIPCHK(hipMemcpyAsync(b->stage[slot].p, static_cast<const char*>(part.dev) + off, nb,
+                                  hipMemcpyDeviceToHost, st));
+            HIPCHK(hipEventRecord(b->stage_ev[slot], st));
+            if (prev_slot >= 0) {
+                HIPCHK(hipEventSynchronize(b->stage_ev[prev_slot]));
+                par_memcpy(prev_host, b->stage[prev_slot].p, prev_n, threads);
+            }
+            prev_host = static_cast<char*>(part.host) + off;
+            prev_n = nb;
+            prev_slot = slot;
+        }
+    }
+    if (prev_slot >= 0) {
+        HIPCHK(hipEventSynchronize(b->stage_ev[prev_slot]));
+        par_memcpy(prev_host, b->stage[prev_slot].p, prev_n, threads);
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return XS_OK;
+}
+
+// The chunks, probes and reductions of one call, enqueued on the first locus' stream; then the
+// outputs' copies to the host.  host_offs: the reads' offsets on the host (n + 1, [0] = 0) or null.
+int mlst_type_run(xs_bank* const* loci, uint32_t n_loci, const Inputs& all, const uint64_t* host_offs, uint32_t step,
+                  uint64_t workspace_bytes, const MlstTypeOut& out) {
+    xs_bank* b0 = loci[0];
+    const hipStream_t s = b0->stream;
+    const uint64_t n = all.n, L = n_loci;
+    uint64_t dmax = 1;
+    for (uint32_t l = 0; l < n_loci; ++l) dmax = std::max(dmax, loci[l]->D);
+    const uint64_t ws = workspace_bytes ? workspace_bytes : kMlstTypeWs;
+    const uint64_t per = std::min<uint64_t>({std::max<uint64_t>(1, ws / (dmax * 4)), n, (1ull << 31) - 1});
+    if (int rc = ws_enter(b0, s)) return rc;
+    if (int rc = b0->hits.ensure(per * dmax * 4)) return rc;
+    if (int rc = b0->best.ensure(n * L * 4 * 3)) return rc;
+    if (out.num_kmers)
+        if (int rc = b0->nk.ensure(n * 8)) return rc;
+    uint32_t* d_rows = b0->hits.as<uint32_t>();
+    uint32_t* d_top = b0->best.as<uint32_t>();
+    uint32_t* d_score = d_top + n * L;
+    uint32_t* d_tied = out.n_tied ? d_score + n * L : nullptr;
+    uint64_t* d_nk = out.num_kmers ? b0->nk.as<uint64_t>() : nullptr;
+    for (uint64_t r0 = 0; r0 < n; r0 += per) {
+        const uint64_t cn = std::min(per, n - r0);
+        // the chunk's own bytes where the host knows the offsets; else the batch's, an upper bound (plans only)
+        const Inputs in{all.seqs, all.seq_bytes, all.offs + r0, cn, host_offs ? host_offs[r0 + cn] - host_offs[r0] : 0};
+        for (uint32_t l = 0; l < n_loci; ++l) {
+            if (int rc = run_query(loci[l], in, step, d_rows, l == 0 && d_nk ? d_nk + r0 : nullptr, nullptr, s)) return rc;
+            const uint64_t o = r0 * L + l;
+            HIPCHK(launch_mlst_top(d_rows, cn, loci[l]->D, d_top + o, d_score + o, d_tied ? d_tied + o : nullptr, L, s));
+        }
+    }
+    if (int rc = ws_leave(b0, s)) return rc;
+    const D2hPart parts[4] = {{out.top, d_top, n * L * 4},
+                              {out.top_score, d_score, n * L * 4},
+                              {out.n_tied, d_tied, d_tied ? n * L * 4 : 0},
+                              {out.num_kmers, d_nk, d_nk ? n * 8 : 0}};
+    return d2h_parts(b0, parts, 4, s);
+}
+
+// However a call ends, nothing enqueued for it may still read the caller's reads once it has returned.
+struct DrainStream {
+    hipStream_t s;
+    ~DrainStream() { (void)hipStreamSynchronize(s); }
+};
+
 }  // namespace
 
 extern "C" {
@@ -887,6 +1055,52 @@ int xs_mlst_query(xs_bank* b, const char* seqs, const uint64_t* offsets, uint64_
         }
         HIPCHK(hipStreamSynchronize(b->stream));
         return XS_OK;
+    });
+}
+
+int xs_mlst_top_device(const uint32_t* d_hits, uint64_t n, uint64_t num_docs, uint32_t* d_top, uint32_t* d_top_score,
+                       uint32_t* d_n_tied, uint64_t out_stride, void* stream) {
+    return xs::guard([&]() -> int {
+        if ((!d_hits || !d_top || !d_top_score) && n) return fail(XS_ERR_ARG, "null argument");
+        if (num_docs == 0 || num_docs > 0xFFFFFFFFull) return fail(XS_ERR_ARG, "num_docs must be in 1 .. 2^32-1");
+        if (out_stride == 0) return fail(XS_ERR_ARG, "out_stride must be >= 1");
+        HIPCHK(launch_mlst_top(d_hits, n, num_docs, d_top, d_top_score, d_n_tied, out_stride,
+                               static_cast<hipStream_t>(stream)));
+        return XS_OK;
+    });
+}
+
+int xs_mlst_type(xs_bank* const* loci, uint32_t n_loci, const char* seqs, const uint64_t* offsets, uint64_t n,
+                 uint32_t step, uint64_t workspace_bytes, uint32_t* top, uint32_t* top_score, uint32_t* n_tied,
+                 uint64_t* num_kmers_out) {
+    return xs::guard([&]() -> int {
+        const MlstTypeOut out{top, top_score, n_tied, num_kmers_out};
+        if (!offsets || (!seqs && n)) return fail(XS_ERR_ARG, "null argument");
+        if (int rc = mlst_type_check(loci, n_loci, n, step, out)) return rc;
+        LociLock lk(loci, n_loci);
+        HIPCHK(hipSetDevice(loci[0]->device));
+        if (n == 0) return XS_OK;
+        DrainStream drain{loci[0]->stream};
+        if (int rc = ws_enter(loci[0], loci[0]->stream)) return rc;
+        Inputs in;
+        if (int rc = upload_reads(loci[0], seqs, offsets, n, loci[0]->stream, &in)) return rc;
+        return mlst_type_run(loci, n_loci, in, static_cast<const uint64_t*>(loci[0]->offs_h.p), step, workspace_bytes,
+                             out);
+    });
+}
+
+int xs_mlst_type_device(xs_bank* const* loci, uint32_t n_loci, const void* d_seqs, uint64_t seq_bytes,
+                        const uint64_t* d_offsets, uint64_t n, uint32_t step, uint64_t workspace_bytes, uint32_t* top,
+                        uint32_t* top_score, uint32_t* n_tied, uint64_t* num_kmers_out) {
+    return xs::guard([&]() -> int {
+        const MlstTypeOut out{top, top_score, n_tied, num_kmers_out};
+        if (n && (!d_seqs || !d_offsets)) return fail(XS_ERR_ARG, "null argument");
+        if (int rc = mlst_type_check(loci, n_loci, n, step, out)) return rc;
+        LociLock lk(loci, n_loci);
+        HIPCHK(hipSetDevice(loci[0]->device));
+        if (n == 0) return XS_OK;
+        const Inputs in{static_cast<const uint8_t*>(d_seqs), seq_bytes, d_offsets, n};
+        return mlst_type_run(loci, n_loci, in, nullptr, step, workspace_bytes, out);
     });
 }
 

@@ -13,6 +13,7 @@ from pathlib import Path
 
 import numpy as np
 
+from ._lib import XS_MLST_NONE
 from .packing import PackedIds
 
 
@@ -340,3 +341,133 @@ class MlstResult:
         output_path = Path(output_path)
         output_path.parent.mkdir(exist_ok=True, parents=True)
         output_path.write_text(dumps(self.to_dict(), indent=4), encoding="utf-8")
+
+
+MLST_UNRELIABLE = "This strain type is not reliable due to low kmer hit rates!"
+
+
+class MlstColumnarResult:
+    """Columnar MLST typing: per record and locus the top allele, its score and
+    how many alleles share that score, and per record the sufficiency flag.
+
+    These are the numbers the reference keeps per record under "Strain type"
+    (``probabilistic_filter_mlst_model.py:272-303``: the first item of each
+    locus' result, and ``has_sufficient_score`` :428-449), 12 bytes per
+    (record, locus) in place of a dictionary of every allele.
+
+    ``top_allele[i, l]`` indexes ``allele_names[l]`` (the locus bank's doc
+    order); ``XS_MLST_NONE`` is the reference's "N/A" (a record of 10 kbp or
+    more none of whose chunks passed at that locus), with score 0 and
+    ``n_tied`` 0.  ``n_tied`` is not in the reference: 1 means the call is
+    unique at that locus.  ``ids`` may be a ``PackedIds``."""
+
+    def __init__(self, scheme_model: str, steps: int, ids, loci: list[str], allele_names: list[list[str]],
+                 locus_size: list[int], top_allele: np.ndarray, top_score: np.ndarray, n_tied: np.ndarray,
+                 input_source: str | None = None):
+        n, L = len(ids), len(loci)
+        self.top_allele = np.ascontiguousarray(top_allele, dtype=np.uint32).reshape(-1, L)
+        self.top_score = np.ascontiguousarray(top_score, dtype=np.uint64).reshape(-1, L)
+        self.n_tied = np.ascontiguousarray(n_tied, dtype=np.uint32).reshape(-1, L)
+        if not (self.top_allele.shape == self.top_score.shape == self.n_tied.shape == (n, L)) or \
+                len(allele_names) != L or len(locus_size) != L:
+            raise ValueError("top_allele, top_score and n_tied must be [len(ids), len(loci)]; "
+                             "allele_names and locus_size need one entry per locus")
+        self.scheme_model = scheme_model
+        self.steps = steps
+        self.ids = ids if isinstance(ids, PackedIds) else list(ids)
+        self.loci = list(loci)
+        self.allele_names = [list(a) for a in allele_names]
+        self.locus_size = [int(s) for s in locus_size]
+        self.input_source = input_source
+        # has_sufficient_score over the columns: some locus' top score >= half its allele length
+        half = 0.5 * np.asarray(self.locus_size, dtype=np.float64)
+        self.sufficient = (self.top_score >= half[None, :]).any(axis=1) if L else np.zeros(n, dtype=bool)
+        self._numbers: list[np.ndarray] | None = None
+
+    def _missing(self) -> np.ndarray:
+        return self.top_allele == XS_MLST_NONE
+
+    def allele_numbers(self) -> np.ndarray:
+        """[n, L] int64: ``int(name.split("_")[-1])`` of every top allele (the
+        reference's ``flattened`` profile, :297-300), -1 for "N/A"."""
+        if self._numbers is None:
+            self._numbers = [np.fromiter((int(a.split("_")[-1]) for a in names), dtype=np.int64, count=len(names))
+                             for names in self.allele_names]
+        out = np.full(self.top_allele.shape, -1, dtype=np.int64)
+        miss = self._missing()
+        for l, nums in enumerate(self._numbers):
+            keep = ~miss[:, l]
+            out[keep, l] = nums[self.top_allele[keep, l]]
+        return out
+
+    def strain_type(self, i: int, resolver=None, scheme_url: str | None = None) -> dict:
+        """The dict ``predict()`` puts under ``hits[id][0]["Strain type"]`` for
+        record i: ``{locus: {allele: score}}`` plus "Attention:" (insufficient
+        scores) or "ST_Name" (``resolver(profile, scheme_url)``; None without a
+        resolver).  ``predict()`` itself fails on a record with an "N/A" locus
+        beside a sufficient one (the reference's ``int("N/A")``, or its string
+        ``result_dict``); for such a record "ST_Name" is None here and the
+        resolver is not called."""
+        res: dict = {}
+        profile: dict | None = {}
+        for l, locus in enumerate(self.loci):
+            a = int(self.top_allele[i, l])
+            if a == XS_MLST_NONE:
+                res[locus] = {"N/A": 0}
+                profile = None
+                continue
+            name = self.allele_names[l][a]
+            res[locus] = {name: int(self.top_score[i, l])}
+            if profile is not None and self.sufficient[i]:
+                profile[locus] = int(name.split("_")[-1])
+        if not self.sufficient[i]:
+            res["Attention:"] = MLST_UNRELIABLE
+        else:
+            res["ST_Name"] = resolver(profile, scheme_url) if resolver and profile is not None else None
+        return res
+
+    def resolve_unique(self, resolver, scheme_url: str | None = None) -> list:
+        """The strain type of every record ("ST_Name" of ``strain_type``; None for
+        an insufficient record or one with an "N/A" locus), with one resolver
+        call per distinct allele-number profile among the sufficient records: a
+        million reads of one strain cost one lookup, not a million."""
+        out: list = [None] * len(self.ids)
+        rows = np.flatnonzero(self.sufficient & ~self._missing().any(axis=1))
+        if rows.size == 0:
+            return out
+        profiles, inverse = np.unique(self.allele_numbers()[rows], axis=0, return_inverse=True)
+        names = [resolver(dict(zip(self.loci, map(int, p))), scheme_url) for p in profiles]
+        for r, u in zip(rows.tolist(), np.asarray(inverse).reshape(-1).tolist()):
+            out[r] = names[u]
+        return out
+
+    def to_mlst_hits(self, resolver=None, scheme_url: str | None = None) -> dict:
+        """``{id: strain_type(i)}``: per-record dictionaries, for small inputs."""
+        return {rid: self.strain_type(i, resolver, scheme_url) for i, rid in enumerate(self.ids)}
+
+    def to_dict(self) -> dict:
+        """The columnar JSON layout: one list per locus and column,
+        aligned with "ids"; allele names spelled out, "N/A" where there is none."""
+        miss = self._missing()
+
+        def names(l: int) -> list[str]:
+            tbl = self.allele_names[l]
+            return ["N/A" if m else tbl[a] for a, m in zip(self.top_allele[:, l].tolist(), miss[:, l].tolist())]
+
+        return {
+            "Scheme": self.scheme_model,
+            "Steps": self.steps,
+            "Input_source": self.input_source,
+            "ids": list(self.ids),
+            "loci": self.loci,
+            "locus_size": self.locus_size,
+            "top_allele": {locus: names(l) for l, locus in enumerate(self.loci)},
+            "top_score": {locus: self.top_score[:, l].tolist() for l, locus in enumerate(self.loci)},
+            "n_tied": {locus: self.n_tied[:, l].tolist() for l, locus in enumerate(self.loci)},
+            "sufficient": self.sufficient.tolist(),
+        }
+
+    def save(self, path: Path | str) -> None:
+        path = Path(path)
+        path.parent.mkdir(exist_ok=True, parents=True)
+        path.write_text(dumps(self.to_dict(), separators=(",", ":")), encoding="utf-8")
