@@ -1,7 +1,8 @@
 """Pure-Python restatement of Biopython's FASTA / FASTQ record parsing.
 
 TEST INFRASTRUCTURE ONLY: the checker for the native reader
-(xspect2_amd/csrc/xs_fastx.cpp, xs_fastx_* in include/xspect_hip.h).  Only
+(the parser in xspect2_amd/csrc/xs_fastx_parse.cpp, behind xs_fastx_* in
+include/xspect_hip.h; the rules are stated at the top of xs_fastx.cpp).  Only
 tests/ may import it.
 
 The reference parses input files with ``Bio.SeqIO.parse(path, "fasta"|"fastq")``

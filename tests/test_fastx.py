@@ -231,3 +231,128 @@ def test_byte_range_parts_of_a_large_file(tmp_path):
     want = ofx.parse_file(p)
     got = [r for i in range(3) for r in _native_part(p, i, 3, 3 << 20, 8)]
     assert got == want
+
+
+# ---- the forks of the FASTQ record walk (xs_fastx_parse.cpp) ------------------------------
+# parse_fastq, the sequential cut point and the wrapped-file detection are written on one
+# walk of a record; each case below takes one of its forks and is checked against the
+# restatement, whole and in byte-range parts.
+
+def _stitched(p, parts, max_bytes=1 << 30, threads=1):
+    return [r for i in range(parts) for r in _native_part(p, i, parts, max_bytes, threads)]
+
+
+def _fastq_with_empty_records(rng, n, wrapped, quality_line) -> bytes:
+    """n records; the first, the last and every 50th have an empty sequence (an empty
+    sequence line, then '+'), followed by an empty quality line or by none."""
+    out = []
+    for i in range(n):
+        if i in (0, n - 1) or i % 50 == 25:
+            out.append(b"@empty_%d e\n\n+\n" % i + (b"\n" if quality_line else b""))
+            continue
+        L = int(rng.integers(1, 200))
+        seq, qual = _pick(rng, b"ACGTN", L), _pick(rng, b"@+IJ", L)
+        w = 60 if wrapped else L
+        out.append(b"@r%d x\n" % i + b"\n".join(seq[j:j + w] for j in range(0, L, w)) + b"\n+\n"
+                   + b"\n".join(qual[j:j + w] for j in range(0, L, w)) + b"\n")
+    return b"".join(out)
+
+
+@pytest.mark.parametrize("quality_line", [True, False])
+@pytest.mark.parametrize("wrapped", [False, True])
+def test_fastq_records_with_an_empty_sequence(tmp_path, wrapped, quality_line):
+    """No quality line is read for an empty sequence: an empty one that follows is a blank
+    line before the next record, in four-line and in wrapped files alike."""
+    p = tmp_path / "e.fastq"
+    p.write_bytes(_fastq_with_empty_records(np.random.default_rng(23), 400, wrapped, quality_line))
+    want = ofx.parse_file(p)
+    assert len(want) == 400 and want[0] == (b"empty_0", b"") and want[-1] == (b"empty_399", b"")
+    assert sum(1 for _, s in want if not s) == 10
+    for mb in (1, 3000, 1 << 30):
+        assert _native(p, mb, 1) == want
+    for parts in (2, 3, 7):
+        assert _stitched(p, parts, 3000 if parts == 3 else 1 << 30) == want, parts
+
+
+def _wrapped_fastq_hard(rng, n, blank) -> bytes:
+    """Wrapped records whose every quality line begins with '@' or '+' (what a cut by
+    pattern would take for a header or a '+' line), with blank lines between records."""
+    out = []
+    for i in range(n):
+        L = int(rng.integers(61, 300))
+        seq, qual = _pick(rng, b"ACGT", L), bytearray(_pick(rng, b"@+IJ", L))
+        for j in range(0, L, 60):
+            qual[j] = b"@+"[(i + j // 60) % 2]
+        out.append(b"@w%d\n" % i + b"\n".join(seq[j:j + 60] for j in range(0, L, 60)) + b"\n+w%d\n" % i
+                   + b"\n".join(bytes(qual[j:j + 60]) for j in range(0, L, 60)) + b"\n")
+        if blank and i % 3 == 0:
+            out.append(b"\n" * (1 + i % 2) if i % 2 else b" \r\n")
+    return b"".join(out)
+
+
+@pytest.mark.parametrize("blank", [False, True])
+def test_wrapped_fastq_quality_lines_that_look_like_headers(tmp_path, blank):
+    p = tmp_path / "w.fastq"
+    p.write_bytes(_wrapped_fastq_hard(np.random.default_rng(29 + blank), 300, blank))
+    want = ofx.parse_file(p)
+    assert len(want) == 300
+    assert _native(p, 1 << 30, 1) == want and _native(p, 2000, 8) == want
+    for parts in (2, 3, 7):
+        assert _stitched(p, parts, 2000 if parts == 3 else 1 << 30, 1 + parts % 3) == want, parts
+
+
+def test_wrapped_fastq_malformed_record_in_a_middle_part(tmp_path):
+    """A quality shorter than its sequence in the middle of a wrapped file opened in three
+    parts: the part before it yields its records, the part that holds it yields the batches
+    before its and then raises the host reader's error, and every part does what the
+    restatement does on the same bytes."""
+    rng = np.random.default_rng(31)
+    good = _wrapped_fastq(rng, 150)
+    bad = b"@short\n" + b"ACGT" * 40 + b"\n+\n" + b"I" * 100 + b"\n"  # then '@w..' lines read as quality
+    p = tmp_path / "m.fastq"
+    data = good + bad + _wrapped_fastq(rng, 150)
+    p.write_bytes(data)
+    with pytest.raises(ValueError, match="Lengths of sequence and quality"):
+        ofx.parse_file(p)
+    # each part's byte range, as its batches report it (text_bytes = the part's end)
+    ends = []
+    for part in range(2):
+        with FastxReader(p, threads=1, part=part, parts=3) as rd:
+            ends.append(rd.next_batch(1000).text_bytes)
+    assert 0 < ends[0] < len(good) < ends[1] < len(data)
+    cuts = [0] + ends + [len(data)]
+    assert _native_part(p, 0, 3) == ofx.parse_fastq(data[:cuts[1]]) and len(_native_part(p, 0, 3)) > 50
+    before = []
+    with pytest.raises(ValueError, match=r"Lengths of sequence and quality values differs \(160 and \d+\)"):
+        with FastxReader(p, threads=1, part=1, parts=3) as rd:
+            for b in rd.batches(1000):
+                before += _rows(b)
+    # the batch that holds the malformed record is lost with it: a window of 1,000 bytes
+    # and the record that crosses its end (a sequence is shorter than 200)
+    held = ofx.parse_fastq(data[cuts[1]:len(good)])
+    assert len(before) > 10 and before == held[:len(before)]
+    assert sum(len(s) for _, s in held[len(before):]) < 1000 + 200
+    with pytest.raises(ValueError, match="Lengths of sequence and quality"):
+        ofx.parse_fastq(data[cuts[1]:cuts[2]])
+    try:
+        want_last = ofx.parse_fastq(data[cuts[2]:])
+    except ValueError:
+        with pytest.raises(ValueError):
+            _native_part(p, 2, 3)
+    else:
+        assert _native_part(p, 2, 3) == want_last
+
+
+def test_fastq_wrapped_only_after_the_detection_window(tmp_path):
+    """The wrapped-file detection looks at the first 1,000 records (or 1 MiB).  A file
+    whose first 1,000 records have four lines and whose record 1,001 is wrapped counts as
+    a four-line file; read whole by one thread it is still parsed by the record rules and
+    yields the restatement's records."""
+    rng = np.random.default_rng(37)
+    p = tmp_path / "late.fastq"
+    p.write_bytes(_fastq_text(rng, 1000) + _wrapped_fastq(rng, 200))
+    assert p.stat().st_size < 1 << 20
+    want = ofx.parse_file(p)
+    assert len(want) == 1200
+    assert _native(p, 1 << 30, 1) == want
+    assert _stitched(p, 1, 1 << 30, 1) == want

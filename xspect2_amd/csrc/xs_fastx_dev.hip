@@ -8,7 +8,7 @@
 //   scan      : tile starts in the line index (hipCUB)
 //   positions : every '\n' position, in text order (block scan per 4 KiB row)
 //   records   : FASTQ, one thread per 4-line record: Biopython's checks
-//               (FastqGeneralIterator, restated in xs_fastx.cpp), spans of the
+//               (FastqGeneralIterator, xs_fastx_parse.cpp), spans of the
 //               sequence, id and title; FASTA, one thread per line: header or
 //               sequence line, the line's kept length
 //   scan      : output offsets of sequences, ids and titles
@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(kFxThreads) fx_positions_kernel(const uint8_t*
 }
 
 // FASTQ: record r = lines 4r .. 4r+3.  The checks are the host reader's
-// (parse_fastq, xs_fastx.cpp), narrowed to the layouts where four lines are
+// (parse_fastq, xs_fastx_parse.cpp), narrowed to the layouts where four lines are
 // exactly one record; anything else sets *bad and the host parses the window.
 __global__ void __launch_bounds__(kFqBlock) fq_records_kernel(const uint8_t* __restrict__ t,
                                                               const uint32_t* __restrict__ nl, uint64_t n,
