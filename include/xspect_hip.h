@@ -274,6 +274,95 @@ int xs_mlst_type_device(xs_bank* const* loci, uint32_t n_loci, const void* d_seq
                         const uint64_t* d_offsets, uint64_t n, uint32_t step, uint64_t workspace_bytes,
                         uint32_t* top, uint32_t* top_score, uint32_t* n_tied, uint64_t* num_kmers_out);
 
+/* ---- MLST typing of contigs: chunk scores and the top allele on the device.
+ * The reference treats a record of 10 kbp and more differently
+ * (probabilistic_filter_mlst_model.py:236-270): per locus, sequence_splitter
+ * (:382-426) cuts it into overlapping chunks of about one allele length, every
+ * chunk is searched on its own, only chunk scores > 50 are kept (get_cobs_result
+ * :362-380) and summed per allele, and the first allele of the stable sort by
+ * -sum is the call (:248-256).  All integers, reproduced exactly:
+ *
+ *   A record of n >= long_len bytes is long.  With the locus' base width w and
+ *   the bank's k: W = w (n < scale10_len), 10 w (n < scale100_len), else 100 w;
+ *   stride S = W - k + 1.
+ *   n >= W: m = (n - W) / S + 1 full chunks, chunk j = bytes [j S, j S + W).
+ *   With r = n - m S (always >= k - 1): r >= k gives one more chunk [m S, n);
+ *   r == k - 1 appends the tail to the last chunk, which becomes
+ *   seq[(m-1) S : n] + seq[n - (k-1) : n], W + k - 1 bytes with its last k - 1
+ *   bytes repeated (the repeat is no window of the record; its junction k-mers
+ *   count).  n < W: one chunk, the whole record.
+ *   Each chunk is probed as a read with the call's step.  A chunk's count for
+ *   an allele takes part only if it is > threshold.  Per (record, allele):
+ *   sum of the participating counts, first = the lowest participating chunk,
+ *   fscore = that chunk's count.
+ *   top = the allele with the largest sum > 0, ties by the lower first, then
+ *   the higher fscore, then the lower doc index (the reference's dict order
+ *   under its stable sort); top_score = that sum; n_tied = the alleles whose sum
+ *   equals it.  No allele with sum > 0: XS_MLST_NONE, 0, 0.
+ *
+ * Records shorter than long_len follow xs_mlst_type's rule. */
+typedef struct xs_mlst_chunk_rule_t {
+    uint64_t long_len;      /* records of >= long_len bytes are chunked (reference: 10000, :236) */
+    uint64_t scale10_len;   /* from here chunks are 10 x the locus width (1000000, :404-407) */
+    uint64_t scale100_len;  /* from here 100 x (10000000, :408-409) */
+    uint32_t threshold;     /* a chunk count takes part only if > threshold (50, :378) */
+    uint32_t reserved;
+} xs_mlst_chunk_rule_t;     /* NULL wherever it is taken: the reference's values */
+
+/* A batch of short reads, contigs or both typed in one call (replaces the loop
+ * over loci, chunks and alleles of probabilistic_filter_mlst_model.py:236-286):
+ * the reads are uploaded once; short records are probed and reduced as by
+ * xs_mlst_type; long records are cut into chunks on the device, the chunks
+ * probed, thresholded, summed and reduced there, per locus in ranges of chunks
+ * whose rows, texts and accumulators stay within a small multiple of
+ * workspace_bytes (0: 4 GiB), a record cut by a range end carrying its sums
+ * over.  No text and no per-record matrix returns to the host.  locus_width:
+ * n_loci base widths w (the model's average_locus_base_pair_size).  Outputs as
+ * xs_mlst_type's; num_kmers_out[r] is the whole record's sampled k-mer count,
+ * for long records too.  XS_ERR_ARG beyond xs_mlst_type's: locus_width NULL or
+ * some width < k, long_len < k, scale10_len > scale100_len, or 2^32 - 64 and
+ * more sequence bytes (a sum could leave uint32). */
+int xs_mlst_type_contigs(xs_bank* const* loci, uint32_t n_loci, const uint64_t* locus_width,
+                         const xs_mlst_chunk_rule_t* rule, const char* seqs, const uint64_t* offsets, uint64_t n,
+                         uint32_t step, uint64_t workspace_bytes, uint32_t* top, uint32_t* top_score,
+                         uint32_t* n_tied, uint64_t* num_kmers_out);
+
+/* The same for reads already in HBM.  host_offsets: the n + 1 offsets on the
+ * host as well (an xs_fastx_dbatch has them), or NULL: the library copies
+ * d_offsets back once, since the lengths decide the chunk geometry. */
+int xs_mlst_type_contigs_device(xs_bank* const* loci, uint32_t n_loci, const uint64_t* locus_width,
+                                const xs_mlst_chunk_rule_t* rule, const void* d_seqs, uint64_t seq_bytes,
+                                const uint64_t* d_offsets, const uint64_t* host_offsets, uint64_t n, uint32_t step,
+                                uint64_t workspace_bytes, uint32_t* top, uint32_t* top_score, uint32_t* n_tied,
+                                uint64_t* num_kmers_out);
+
+/* The splitter alone (sequence_splitter, probabilistic_filter_mlst_model.py:382-426).
+ * xs_mlst_split_size: from the host, the chunks and chunk text bytes that n_long
+ * records of the given lengths make at base width `width` (closed forms; every
+ * listed record is split, whatever long_len).  xs_mlst_split_device: the chunk
+ * texts of records d_long_index[0 .. n_long) of the device reads, repeated
+ * tails included, packed into d_chunk_seqs (chunk_bytes + 64 bytes: 64 zero
+ * bytes follow the last chunk, as the probes expect), their n_chunks + 1
+ * offsets, and per listed record the index of its first chunk (n_long + 1
+ * entries, the last = n_chunks).  Returns once they are written.  XS_ERR_ARG:
+ * width < k, k = 0, long_len < k, scale10_len > scale100_len. */
+int xs_mlst_split_size(const uint64_t* lengths, uint64_t n_long, uint64_t width, uint32_t k,
+                       const xs_mlst_chunk_rule_t* rule, uint64_t* n_chunks, uint64_t* chunk_bytes);
+int xs_mlst_split_device(const void* d_seqs, const uint64_t* d_offsets, const uint32_t* d_long_index,
+                         uint64_t n_long, uint64_t width, uint32_t k, const xs_mlst_chunk_rule_t* rule,
+                         void* d_chunk_seqs, uint64_t* d_chunk_offsets, uint64_t* d_owner_begin, void* stream);
+
+/* The reduction alone (probabilistic_filter_mlst_model.py:248-256, 362-380) over
+ * a device matrix of chunk rows (n_chunks x num_docs uint32, 4-byte aligned):
+ * owner o owns rows [d_owner_begin[o], d_owner_begin[o + 1]) (n_owners + 1
+ * non-decreasing entries from 0 to n_chunks; a row's index is its chunk index),
+ * an owner without rows gives XS_MLST_NONE, 0, 0.  Owner o's values are written
+ * at index o * out_stride of d_top, d_top_score and d_n_tied (may be NULL), as
+ * by xs_mlst_top_device.  Returns once they are written. */
+int xs_mlst_chunk_top_device(const uint32_t* d_hits, uint64_t n_chunks, uint64_t num_docs,
+                             const uint64_t* d_owner_begin, uint64_t n_owners, uint32_t threshold, uint32_t* d_top,
+                             uint32_t* d_top_score, uint32_t* d_n_tied, uint64_t out_stride, void* stream);
+
 /* Record HIP events around the probe kernel of every query on this handle. */
 int xs_bank_set_profiling(xs_bank* bank, int on);
 /* Duration of the probe kernel of the last profiled query, milliseconds. */

@@ -3,6 +3,11 @@ new one in one run on one GPU:
 
     python tools/mlst_typing_bench.py [--reads 1000000] [--out FILE] [--time-limit 900]
 
+and the assembly leg, ``predict_columnar`` over a FASTA of contigs, on this
+checkout and on another one (the parent commit, built beforehand) in one run:
+
+    python tools/mlst_typing_bench.py --assembly --parent-root DIR [--genomes 20] [--out FILE]
+
 Banks and reads follow tests/test_gpu_fullsize.py::test_config4_mlst_full_size:
 7 loci x 1430 alleles of 400-600 bp (COBS compact, k = 31, one hash, fpr 0.001,
 64-byte pages), error-free 150 bp windows of random alleles.  Three legs, each
@@ -21,14 +26,25 @@ query_device into an n x D device matrix), the reduction alone over that matrix
 sizes.  Before timing, legs b and c must agree, and equal numpy's argmax / max /
 count over leg a's rows on a sample of reads.  Prints one JSON line (and writes
 it to --out).  The run ends itself after --time-limit seconds.
+
+The assembly leg writes one synthetic FASTA (--genomes genomes of --genome-mbp
+Mbp each, cut into contigs of 20-500 kbp, 80 columns per line, one allele of
+every locus embedded per genome; the same 7 x 1430 alleles, k 31) and starts one
+fresh child process per checkout.  Each child builds the same banks from the
+same seed, wraps them in a ProbabilisticFilterMlstSchemeModel and times
+``predict_columnar(path)`` (medians after warm-up, host clock around the call,
+which returns synchronised); the children's columns must be identical.
 """
 from __future__ import annotations
 
 import argparse
+import hashlib
 import json
 import signal
 import statistics
+import subprocess
 import sys
+import tempfile
 import time
 from pathlib import Path
 
@@ -40,15 +56,11 @@ sys.path.insert(0, str(ROOT))
 K, LOCI, ALLELES, PAGE, READ_LEN = 31, 7, 1430, 64, 150
 
 
-def make_scheme(torch, dev, rng):
-    """The loci banks, built on the device, and their alleles padded to one array."""
-    from xspect2_amd.bank import Bank, cobs_signature_size
+def make_alleles(rng):
+    """Per locus its alleles (uint8 arrays), sorted by size as a COBS compact bank stores its docs."""
     acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
-    s = torch.cuda.current_stream(dev).cuda_stream
-    banks = []
-    padded = np.zeros((LOCI, ALLELES, 620), dtype=np.uint8)
-    sizes = np.zeros((LOCI, ALLELES), dtype=np.int64)
-    for li in range(LOCI):
+    loci = []
+    for _ in range(LOCI):
         base = acgt[rng.integers(0, 4, 620)]
         alleles = []
         for _ in range(ALLELES):
@@ -56,7 +68,19 @@ def make_scheme(torch, dev, rng):
             pos = rng.integers(0, a.size, int(rng.integers(0, 12)))
             a[pos] = acgt[(np.searchsorted(acgt, a[pos]) + 1) % 4]
             alleles.append(a)
-        alleles.sort(key=lambda a: a.size)  # COBS compact: docs sorted by size
+        alleles.sort(key=lambda a: a.size)
+        loci.append(alleles)
+    return loci
+
+
+def make_scheme(torch, dev, rng):
+    """The loci banks, built on the device, and their alleles padded to one array."""
+    from xspect2_amd.bank import Bank, cobs_signature_size
+    s = torch.cuda.current_stream(dev).cuda_stream
+    banks = []
+    padded = np.zeros((LOCI, ALLELES, 620), dtype=np.uint8)
+    sizes = np.zeros((LOCI, ALLELES), dtype=np.int64)
+    for li, alleles in enumerate(make_alleles(rng)):
         per = 8 * PAGE
         sig = [cobs_signature_size(max(a.size for a in alleles[g:g + per]) - K + 1, 1, 0.001)
                for g in range(0, ALLELES, per)]
@@ -96,8 +120,101 @@ def timed(fn, warmup, repeats, sync):
             "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "warmup": warmup, "repeats": repeats}
 
 
+# ---------------------------------------------------------------- the assembly leg
+def write_assembly(path: Path, rng, loci, genomes: int, genome_bp: int) -> dict:
+    """A FASTA of `genomes` genomes cut into contigs of 20-500 kbp, one allele of every locus per genome."""
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    n_contigs = total = 0
+    with open(path, "wb") as f:
+        for g in range(genomes):
+            lens = []
+            while sum(lens) < genome_bp:
+                lens.append(int(rng.integers(20_000, 500_001)))
+            contigs = [acgt[rng.integers(0, 4, n)] for n in lens]
+            for alleles in loci:
+                a = alleles[int(rng.integers(0, len(alleles)))]
+                c = contigs[int(rng.integers(0, len(contigs)))]
+                pos = int(rng.integers(0, c.size - a.size))
+                c[pos:pos + a.size] = a
+            for ci, c in enumerate(contigs):
+                f.write(f">g{g}_c{ci}\n".encode())
+                full = c.size // 80 * 80
+                lines = np.full((full // 80, 81), ord("\n"), dtype=np.uint8)
+                lines[:, :80] = c[:full].reshape(-1, 80)
+                f.write(lines.tobytes())
+                if c.size > full:
+                    f.write(c[full:].tobytes() + b"\n")
+                n_contigs += 1
+                total += c.size
+    return {"genomes": genomes, "contigs": n_contigs, "bases": total, "file_bytes": path.stat().st_size}
+
+
+def assembly_child(a) -> int:
+    """Time predict_columnar(a.fasta) with the package of checkout a.root; one JSON line."""
+    sys.path.insert(0, str(a.root))
+    import torch
+    from xspect2_amd import _lib
+    from xspect2_amd.probabilistic_filter_mlst_model import ProbabilisticFilterMlstSchemeModel
+
+    assert Path(_lib.__file__).resolve().is_relative_to(Path(a.root).resolve()), _lib.__file__
+    dev = torch.device("cuda", 0)
+    banks, _, sizes = make_scheme(torch, dev, np.random.default_rng(4242))
+    m = ProbabilisticFilterMlstSchemeModel(K, "MLST (bench)", Path(a.fasta).parent, "https://example/schemes/1", "bench")
+    m.indices = banks
+    m.loci = {f"locus{li}": ALLELES for li in range(LOCI)}
+    m.avg_locus_bp_size = [int(sizes[li, 0]) for li in range(LOCI)]
+    res = m.predict_columnar(Path(a.fasta))
+    digest = hashlib.sha256()
+    for col in (res.top_allele, res.top_score, res.n_tied):
+        digest.update(np.ascontiguousarray(col).tobytes())
+    t = timed(lambda: m.predict_columnar(Path(a.fasta)), a.warmup, a.repeats, lambda: torch.cuda.synchronize(dev))
+    t.update({"build_id": _lib.build_id(), "device": torch.cuda.get_device_name(dev),
+              "records": int(res.top_allele.shape[0]), "records_with_a_call": int((res.n_tied > 0).any(axis=1).sum()),
+              "columns_sha256": digest.hexdigest()})
+    print(json.dumps(t))
+    m.close()
+    return 0
+
+
+def assembly_leg(a) -> int:
+    rng = np.random.default_rng(4242)
+    loci = make_alleles(rng)
+    with tempfile.TemporaryDirectory() as tmp:
+        fasta = Path(tmp) / "assembly.fasta"
+        info = write_assembly(fasta, rng, loci, a.genomes, int(a.genome_mbp * 1e6))
+        runs = {}
+        for name, root in (("parent", a.parent_root), ("this", ROOT)):
+            cmd = [sys.executable, str(Path(__file__).resolve()), "--assembly-child", "--root", str(root), "--fasta",
+                   str(fasta), "--warmup", str(a.warmup), "--repeats", str(a.repeats)]
+            out = subprocess.run(cmd, capture_output=True, text=True, timeout=a.time_limit)
+            if out.returncode != 0:
+                sys.stderr.write(out.stdout + out.stderr)
+                return 1
+            runs[name] = json.loads(out.stdout.strip().splitlines()[-1])
+            print(f"{name}: median {runs[name]['median_ms']} ms", file=sys.stderr, flush=True)
+    same = runs["parent"]["columns_sha256"] == runs["this"]["columns_sha256"]
+    line = {"tool": "mlst_typing_bench --assembly", "input": info,
+            "config": {"loci": LOCI, "alleles_per_locus": ALLELES, "k": K, "page_size": PAGE, "step": 1},
+            "parent": runs["parent"], "this": runs["this"], "same_columns": same,
+            "this_over_parent_speedup": round(runs["parent"]["median_ms"] / runs["this"]["median_ms"], 2),
+            "clock": "host perf_counter around predict_columnar(path), which returns synchronised; one process per checkout"}
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        a.out.parent.mkdir(parents=True, exist_ok=True)
+        a.out.write_text(text + "\n")
+    return 0 if same else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--assembly", action="store_true", help="the assembly leg instead of the read legs")
+    ap.add_argument("--parent-root", type=Path, default=None, help="assembly leg: the other checkout (built)")
+    ap.add_argument("--genomes", type=int, default=20)
+    ap.add_argument("--genome-mbp", type=float, default=4.0)
+    ap.add_argument("--assembly-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--root", type=Path, default=ROOT, help=argparse.SUPPRESS)
+    ap.add_argument("--fasta", type=Path, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--reads", type=int, default=1_000_000)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=10)
@@ -114,6 +231,12 @@ def main():
 
     signal.signal(signal.SIGALRM, too_long)
     signal.alarm(a.time_limit)
+    if a.assembly_child:
+        return assembly_child(a)
+    if a.assembly:
+        if a.parent_root is None:
+            raise SystemExit("mlst_typing_bench: --assembly needs --parent-root")
+        return assembly_leg(a)
 
     import torch
     from xspect2_amd import _lib

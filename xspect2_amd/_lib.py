@@ -73,6 +73,17 @@ class ProbeOptions(ctypes.Structure):
     ]
 
 
+class MlstChunkRule(ctypes.Structure):
+    """xs_mlst_chunk_rule_t: when a record is chunked and how (defaults = the reference's constants)."""
+    _fields_ = [
+        ("long_len", ctypes.c_uint64),
+        ("scale10_len", ctypes.c_uint64),
+        ("scale100_len", ctypes.c_uint64),
+        ("threshold", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 class FastxBatch(ctypes.Structure):
     _fields_ = [
         ("n", ctypes.c_uint64),
@@ -149,6 +160,12 @@ SIGNATURES = {
     "xs_mlst_top_device": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp]),
     "xs_mlst_type": (_int, [_vp, _u32, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp]),
     "xs_mlst_type_device": (_int, [_vp, _u32, _vp, _u64, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp]),
+    "xs_mlst_type_contigs": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp]),
+    "xs_mlst_type_contigs_device": (_int, [_vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp,
+                                           _vp]),
+    "xs_mlst_split_size": (_int, [_vp, _u64, _u64, _u32, _vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "xs_mlst_split_device": (_int, [_vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "xs_mlst_chunk_top_device": (_int, [_vp, _u64, _u64, _vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp]),
     "xs_bank_set_profiling": (_int, [_vp, _int]),
     "xs_bank_last_probe_ms": (_int, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "xs_bank_probe_stats": (_int, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double),

@@ -547,10 +547,14 @@ class DeviceReads:
     reader batch is (``mlst_type``, ``Bank.query``); the caller keeps the
     tensors complete (synchronised) and alive for the call."""
 
-    def __init__(self, seqs, seq_bytes: int, offsets, n: int, max_len: int = 0):
+    def __init__(self, seqs, seq_bytes: int, offsets, n: int, max_len: int = 0, host_offsets=None):
         self._keep = (seqs, offsets)
         self.seqs_ptr, self.offsets_ptr = _dptr(seqs) or 0, _dptr(offsets) or 0
         self.seq_bytes, self.n, self.max_len = int(seq_bytes), int(n), int(max_len)
+        # the same n + 1 offsets on the host, where the caller has them (mlst_type_contigs then copies none back)
+        self.host_offsets = None if host_offsets is None else np.ascontiguousarray(host_offsets, dtype=np.uint64)
+        if self.host_offsets is not None and self.host_offsets.size != self.n + 1:
+            raise ValueError("host_offsets must hold n + 1 entries")
 
     def check_valid(self) -> None:
         pass
@@ -587,6 +591,83 @@ def mlst_type(banks: Sequence[Bank], reads, step: int = 1, workspace_bytes: int 
     return top, score, tied, nk
 
 
+def _chunk_rule(rule):
+    """None (the reference's constants), a _lib.MlstChunkRule, or (long_len, scale10_len, scale100_len, threshold)."""
+    if rule is None or isinstance(rule, _lib.MlstChunkRule):
+        return rule
+    long_len, scale10, scale100, threshold = rule
+    return _lib.MlstChunkRule(int(long_len), int(scale10), int(scale100), int(threshold), 0)
+
+
+def mlst_type_contigs(banks: Sequence[Bank], reads, widths, step: int = 1, workspace_bytes: int = 0, rule=None):
+    """xs_mlst_type_contigs: short reads, contigs or both typed against every locus
+    bank in one call.  Records below the rule's long_len (10 kbp) follow
+    ``mlst_type``; longer ones are cut on the device into the reference's
+    overlapping chunks per locus (widths[l]: the locus' base width, the model's
+    ``avg_locus_bp_size``), the chunks probed there, their counts above the
+    threshold summed per allele and reduced to the top allele (XS_MLST_NONE, 0, 0
+    where no chunk passes).  Same kinds of ``reads`` and the same four arrays as
+    ``mlst_type``; num_kmers is the whole record's count.  rule: None, a
+    ``_lib.MlstChunkRule`` or (long_len, scale10_len, scale100_len, threshold)."""
+    banks = list(banks)
+    if step < 1:
+        raise ValueError("step must be >= 1")
+    dev = _device_batch(reads)
+    if dev:
+        reads.check_valid()
+    pr = reads if dev or isinstance(reads, PackedReads) else pack_sequences(reads)
+    n, L = pr.n, len(banks)
+    w = np.ascontiguousarray(widths, dtype=np.uint64)
+    if w.size != L:
+        raise ValueError("one width per locus bank")
+    r = _chunk_rule(rule)
+    rule_p = ctypes.byref(r) if r is not None else None
+    handles = (ctypes.c_void_p * max(L, 1))(*[b.handle.value for b in banks])
+    top, score, tied = (_HOST_POOL.empty((n, L), np.uint32) for _ in range(3))
+    nk = np.empty(n, dtype=np.uint64)
+    outs = (_ptr(top) or None, _ptr(score) or None, _ptr(tied) or None, _ptr(nk) or None)
+    if dev:
+        ho = getattr(reads, "host_offsets", None)
+        if ho is None and hasattr(reads, "offsets"):  # a device reader batch keeps its offsets on the host too
+            ho = np.ascontiguousarray(reads.offsets, dtype=np.uint64)
+        check(load().xs_mlst_type_contigs_device(handles, L, _ptr(w), rule_p, pr.seqs_ptr or None, pr.seq_bytes,
+                                                 pr.offsets_ptr or None, _ptr(ho) if ho is not None else None, n,
+                                                 step, workspace_bytes, *outs))
+    else:
+        check(load().xs_mlst_type_contigs(handles, L, _ptr(w), rule_p, _ptr(pr.buf) or None, _ptr(pr.offsets), n,
+                                          step, workspace_bytes, *outs))
+    return top, score, tied, nk
+
+
+def mlst_split_size(lengths, width: int, k: int, rule=None) -> tuple[int, int]:
+    """xs_mlst_split_size: (chunks, chunk text bytes) of records of these lengths at base width `width`."""
+    ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+    r = _chunk_rule(rule)
+    nc, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(load().xs_mlst_split_size(_ptr(ln) or None, ln.size, width, k, ctypes.byref(r) if r is not None else None,
+                                    ctypes.byref(nc), ctypes.byref(nb)))
+    return int(nc.value), int(nb.value)
+
+
+def mlst_split_device(seqs, offsets, long_index, n_long: int, width: int, k: int, chunk_seqs, chunk_offsets,
+                      owner_begin, rule=None, stream: int | None = None) -> None:
+    """xs_mlst_split_device: the chunk texts (``mlst_split_size`` bytes + 64), their
+    offsets and each listed record's first chunk, written to device tensors."""
+    r = _chunk_rule(rule)
+    check(load().xs_mlst_split_device(_dptr(seqs), _dptr(offsets), _dptr(long_index), n_long, width, k,
+                                      ctypes.byref(r) if r is not None else None, _dptr(chunk_seqs),
+                                      _dptr(chunk_offsets), _dptr(owner_begin), stream))
+
+
+def mlst_chunk_top_device(hits, n_chunks: int, num_docs: int, owner_begin, n_owners: int, threshold: int, top,
+                          top_score, n_tied=None, out_stride: int = 1, stream: int | None = None) -> None:
+    """xs_mlst_chunk_top_device: per owner of rows [owner_begin[o], owner_begin[o + 1])
+    of a device matrix of chunk rows, the top allele of the summed counts above
+    `threshold`, its sum and the alleles sharing it, at index o * out_stride."""
+    check(load().xs_mlst_chunk_top_device(_dptr(hits), n_chunks, num_docs, _dptr(owner_begin), n_owners, threshold,
+                                          _dptr(top), _dptr(top_score), _dptr(n_tied), out_stride, stream))
+
+
 def gather_reads_device(seqs, offsets, index, m: int, out_seqs, out_offsets, stream: int | None = None) -> None:
     """xs_gather_reads_device: out read j = read index[j] at out_offsets[j]."""
     check(load().xs_gather_reads_device(_dptr(seqs), _dptr(offsets), _dptr(index), m, _dptr(out_seqs),
@@ -610,4 +691,5 @@ def _dptr(x) -> int | None:
 
 
 __all__ = ["Bank", "bloom_parameters", "cobs_signature_size", "KIND_NAMES", "pinned_empty", "max_kmers", "probe_kernel_names",
-           "mlst_top_device", "mlst_type", "DeviceReads", "XS_BANK_COBS_CLASSIC", "XS_BANK_COBS_COMPACT", "XS_BANK_RBLOOM", "_lib"]
+           "mlst_top_device", "mlst_type", "mlst_type_contigs", "mlst_split_size", "mlst_split_device",
+           "mlst_chunk_top_device", "DeviceReads", "XS_BANK_COBS_CLASSIC", "XS_BANK_COBS_COMPACT", "XS_BANK_RBLOOM", "_lib"]

@@ -162,6 +162,10 @@ struct xs_bank {
     xs::PinnedBuf cut_ofs;          // device-read batches: read offsets at the chunk cuts
     xs::PinnedBuf offs_h;           // host batches: the read offsets rebased to 0, for their H2D copy
     xs::DevBuf small_d;
+    // MLST typing of contigs (mlst_contigs_run): a range's chunk texts, their offsets and accumulators, the call's
+    // chunk runs, and for a batch of many short runs the compacted short reads with their index and outputs
+    xs::DevBuf mc_text, mc_offs, mc_sum, mc_key, mc_runs, mc_short, mc_idx, mc_out;
+    xs::PinnedBuf mc_runs_h, mc_idx_h;
     hipEvent_t hstage_ev[2] = {nullptr, nullptr};
     hipStream_t copy_stream = nullptr, d2h_stream = nullptr;
     std::vector<hipEvent_t> chunk_ev;  // probe of batch chunk i done
@@ -181,7 +185,8 @@ struct xs_bank {
     xs_bank(int device_, int kind_) : kind(kind_), device(device_) {
         for (xs::DevBuf* d : {&seqs, &offs, &nseg, &unit_ofs, &unit_read, &n_units, &scan_tmp, &nk, &hits, &partials,
                               &totals, &tmp, &best, &narrow, &ovf, &rows_read, &pk_nkc, &pk_kofs, &pk_scan, &pk_entries,
-                              &pk_tbl, &pk_miss, &pk_aux, &bloom_tot}) {
+                              &pk_tbl, &pk_miss, &pk_aux, &bloom_tot, &mc_text, &mc_offs, &mc_sum, &mc_key, &mc_runs,
+                              &mc_short, &mc_idx, &mc_out}) {
             d->guard_ev = &ws_ev;
             d->guard_used = &ws_used;
             d->acct = &ws_acct;

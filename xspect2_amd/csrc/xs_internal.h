@@ -240,6 +240,87 @@ hipError_t launch_best_doc(const uint32_t* hits, uint64_t n, uint64_t D, uint32_
 hipError_t launch_mlst_top(const uint32_t* hits, uint64_t n, uint64_t D, uint32_t* top, uint32_t* top_score,
                            uint32_t* n_tied, uint64_t out_stride, hipStream_t s);
 
+// ---- MLST typing of contigs (xs_mlst_chunks.hip) ---------------------------------
+// The reference's sequence_splitter (probabilistic_filter_mlst_model.py:382-426) as closed forms
+// of a record's length n, the chunk width W and k (W >= k): m full chunks at stride S = W - k + 1,
+// then either one more chunk of the remaining r >= k bytes, or (r == k - 1) the last full chunk
+// with its own final k - 1 bytes appended again.  A record shorter than W is one chunk.
+struct MlstRecGeom {
+    uint64_t S;       // stride of the chunk starts
+    uint64_t m;       // full chunks (0: n < W)
+    uint64_t chunks;  // m + 1 (a tail chunk, or the whole short record) or m (repeated tail)
+    uint64_t bytes;   // all chunk texts together
+};
+__host__ __device__ inline uint64_t mlst_chunk_width(uint64_t n, uint64_t w, uint64_t scale10, uint64_t scale100) {
+    return n < scale10 ? w : n < scale100 ? 10 * w : 100 * w;
+}
+__host__ __device__ inline MlstRecGeom mlst_rec_geom(uint64_t n, uint64_t W, uint32_t k) {
+    MlstRecGeom g;
+    g.S = W - k + 1;
+    if (n < W) {
+        g.m = 0;
+        g.chunks = 1;
+        g.bytes = n;
+        return g;
+    }
+    g.m = (n - W) / g.S + 1;
+    const uint64_t r = n - g.m * g.S;  // >= k - 1
+    g.chunks = r >= k ? g.m + 1 : g.m;
+    g.bytes = g.m * W + (r >= k ? r : (uint64_t)k - 1);
+    return g;
+}
+// Bytes of chunk j of such a record (j < chunks).
+__host__ __device__ inline uint64_t mlst_chunk_len(const MlstRecGeom& g, uint64_t n, uint64_t W, uint32_t k,
+                                                   uint64_t j) {
+    if (g.m == 0) return n;
+    if (j == g.m) return n - g.m * g.S;
+    return j + 1 == g.chunks ? W + k - 1 : W;
+}
+
+// One run of consecutive chunks of one record, as the splitter and the reductions take it: `rows`
+// chunks starting at the record's chunk j0 become hit rows [row0, row0 + rows) of the launch and
+// `out` is where the first of them starts in the chunk text (all but a record's last chunk are W
+// bytes).  An array of runs ends with a sentinel whose row0 / out are the launch's totals.
+struct MlstChunkRun {
+    uint64_t row0;  // first: the reductions search the runs' row0 at a stride of sizeof(MlstChunkRun) / 8
+    uint64_t src;   // the record's first byte in the reads
+    uint64_t n;     // the record's length
+    uint64_t W;
+    uint64_t j0;
+    uint64_t out;
+    uint64_t rec;   // the record's row in the outputs
+    uint64_t pad;
+};
+constexpr uint32_t kMlstRunWords = sizeof(MlstChunkRun) / 8;
+
+// Runs of whole records from their device offsets: run e is record index[e] (W by mlst_chunk_width
+// of its length), owner_begin[e] its first chunk; owner_begin[m] and the sentinel carry the totals.
+hipError_t launch_mlst_runs(const uint64_t* offs, const uint32_t* index, uint64_t m, uint64_t w, uint32_t k,
+                            uint64_t scale10, uint64_t scale100, MlstChunkRun* runs, uint64_t* owner_begin,
+                            hipStream_t s);
+// The chunk texts of `n_runs` runs (nc chunks in all) packed into `text`, their nc + 1 offsets,
+// and kPad zero bytes behind the last chunk.
+hipError_t launch_mlst_split(const uint8_t* seqs, const MlstChunkRun* runs, uint64_t n_runs, uint64_t nc, uint32_t k,
+                             uint8_t* text, uint64_t* chunk_offs, hipStream_t s);
+// One pass over nc x D chunk rows: per (owner, doc) the sum of the counts > threshold and the
+// minimum of (chunk_base + row) << 32 | (0xFFFFFFFF - count) over them (the first passing chunk,
+// then the higher count).  Owner o holds rows [begin[o * stride], begin[(o + 1) * stride]);
+// sum (zeroed) and key (all ones) are n_owners x D.
+hipError_t launch_mlst_chunk_acc(const uint32_t* hits, uint64_t nc, uint64_t D, const uint64_t* begin,
+                                 uint32_t stride, uint64_t n_owners, uint32_t threshold, uint64_t chunk_base,
+                                 unsigned long long* sum, unsigned long long* key, hipStream_t s);
+// Per owner row of D (sum, key): the doc with the largest sum > 0, ties by the lower key, then
+// the lower doc; its sum; the docs sharing that sum.  No doc with sum > 0: kMlstNone, 0, 0.  Owner
+// o writes at out[row * out_stride], row = rec ? rec[o * rec_stride] : o.
+constexpr uint32_t kMlstNone = 0xFFFFFFFFu;
+hipError_t launch_mlst_owner_top(const unsigned long long* sum, const unsigned long long* key, uint64_t n_owners,
+                                 uint64_t D, const uint64_t* rec, uint32_t rec_stride, uint32_t* top,
+                                 uint32_t* top_score, uint32_t* n_tied, uint64_t out_stride, hipStream_t s);
+// dst[index[j] * cols + c] = src[j * cols + c] for three m x cols arrays at once.
+hipError_t launch_mlst_scatter_rows(const uint32_t* index, uint64_t m, uint64_t cols, const uint32_t* src0,
+                                    const uint32_t* src1, const uint32_t* src2, uint32_t* dst0, uint32_t* dst1,
+                                    uint32_t* dst2, hipStream_t s);
+
 // dst[i] = src[i] as uint8 (hit_bytes 1) or uint16 (2); the caller guarantees the values fit.
 hipError_t launch_narrow_hits(const uint32_t* src, void* dst, uint64_t n, int hit_bytes, hipStream_t s,
                               uint32_t* overflow = nullptr);

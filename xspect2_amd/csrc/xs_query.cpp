@@ -780,6 +780,252 @@ struct DrainStream {
     ~DrainStream() { (void)hipStreamSynchronize(s); }
 };
 
+// ---- MLST typing of contigs: chunked, probed, summed and reduced on the device ----
+// Records of long_len bytes and more follow the reference's chunk rule (xspect_hip.h), the others
+// mlst_type_run's.  Short records are probed where they lie, run by run of consecutive records (or,
+// when a batch interleaves so many runs that their launches would dominate, compacted once by
+// gather_reads_kernel and their outputs scattered back).  Per locus the long records' chunks are
+// numbered through and processed in ranges of at most R chunks (R rows of the widest locus within
+// the workspace) and about as many text bytes: the splitter writes the range's chunk texts, the
+// probe its rows, one pass adds them to the per-record accumulators and a wave per finished record
+// writes its call.  A record cut by a range end keeps its accumulators in slot 0 of the next range.
+// The host's part is the chunk runs, closed forms of the lengths: O(long records + ranges) per locus.
+constexpr xs_mlst_chunk_rule_t kReferenceRule{10000, 1000000, 10000000, 50, 0};
+constexpr size_t kMaxShortRuns = 64;  // more runs of short records than this: compact them first
+
+int chunk_rule_check(const xs_mlst_chunk_rule_t* rule, xs_mlst_chunk_rule_t* out) {
+    *out = rule ? *rule : kReferenceRule;
+    if (out->scale10_len > out->scale100_len) return fail(XS_ERR_ARG, "scale10_len must be <= scale100_len");
+    return XS_OK;
+}
+
+// The argument errors of xs_mlst_type_contigs / _device that need no device, then those that need the loci's k.
+int mlst_contigs_check(xs_bank* const* loci, uint32_t n_loci, const uint64_t* width, const xs_mlst_chunk_rule_t* rule_in,
+                       uint64_t seq_bytes, uint64_t n, uint32_t step, const MlstTypeOut& out,
+                       xs_mlst_chunk_rule_t* rule) {
+    if (!width) return fail(XS_ERR_ARG, "null argument (locus_width)");
+    if (int rc = chunk_rule_check(rule_in, rule)) return rc;
+    if (seq_bytes >= (1ull << 32) - 64)
+        return fail(XS_ERR_ARG, "at most 2^32-65 sequence bytes per call (a summed score must fit uint32)");
+    if (int rc = mlst_type_check(loci, n_loci, n, step, out)) return rc;
+    const uint32_t k = loci[0]->k;
+    for (uint32_t l = 0; l < n_loci; ++l)
+        if (width[l] < k)
+            return fail(XS_ERR_ARG, "locus_width[%u] = %llu is below k = %u", l, (unsigned long long)width[l], k);
+    if (rule->long_len < k) return fail(XS_ERR_ARG, "long_len must be >= k = %u", k);
+    return XS_OK;
+}
+
+// n reads [r0, r0 + n) probed against every locus in pieces of `per` reads, each piece's rows reduced into
+// columns of the outputs whose row 0 is the first read's (top / score / tied point at it).
+int mlst_type_span(xs_bank* const* loci, uint32_t n_loci, const Inputs& all, const uint64_t* ho, uint64_t r0, uint64_t n,
+                   uint64_t per, uint32_t step, uint32_t* d_rows, uint32_t* top, uint32_t* score, uint32_t* tied,
+                   hipStream_t s) {
+    const uint64_t L = n_loci;
+    for (uint64_t a = 0; a < n; a += per) {
+        const uint64_t cn = std::min(per, n - a);
+        const Inputs in{all.seqs, all.seq_bytes, all.offs + r0 + a, cn, ho[r0 + a + cn] - ho[r0 + a]};
+        for (uint32_t l = 0; l < n_loci; ++l) {
+            if (int rc = run_query(loci[l], in, step, d_rows, nullptr, nullptr, s)) return rc;
+            const uint64_t o = a * L + l;
+            HIPCHK(launch_mlst_top(d_rows, cn, loci[l]->D, top + o, score + o, tied ? tied + o : nullptr, L, s));
+        }
+    }
+    return XS_OK;
+}
+
+// One range of one locus: runs [run0, run0 + n_runs) of the call's run array (a sentinel follows them).
+struct ChunkRange {
+    uint64_t run0, n_runs, nc, bytes, chunk_base;
+    bool carry_in, carry_out;  // its first run continues a record / its last run's record goes on
+};
+
+// The ranges of one locus appended to `ranges`, their runs to `runs`.  ho: the reads' host offsets.
+void cut_chunk_ranges(const std::vector<uint64_t>& longs, const uint64_t* ho, uint64_t w, uint32_t k,
+                      const xs_mlst_chunk_rule_t& rule, uint64_t row_cap, uint64_t text_cap,
+                      std::vector<MlstChunkRun>* runs, std::vector<ChunkRange>* ranges) {
+    uint64_t run0 = runs->size(), cu = 0, bu = 0, base = 0;
+    bool carry_in = false;
+    auto close = [&](bool carry_out) {
+        runs->push_back(MlstChunkRun{cu, 0, 0, 0, 0, bu, 0, 0});
+        ranges->push_back(ChunkRange{run0, runs->size() - 1 - run0, cu, bu, base, carry_in, carry_out});
+        base += cu;
+        run0 = runs->size();
+        cu = bu = 0;
+        carry_in = carry_out;
+    };
+    for (uint64_t rec : longs) {
+        const uint64_t n = ho[rec + 1] - ho[rec];
+        const uint64_t W = mlst_chunk_width(n, w, rule.scale10_len, rule.scale100_len);
+        const MlstRecGeom g = mlst_rec_geom(n, W, k);
+        for (uint64_t j = 0; j < g.chunks;) {
+            uint64_t fit = text_cap > bu ? (text_cap - bu) / W : 0;  // a record's last chunk may exceed W by k - 1
+            if (cu == 0) fit = std::max<uint64_t>(fit, 1);           // a range takes at least one chunk
+            const uint64_t take = std::min({g.chunks - j, row_cap - cu, fit});
+            if (take == 0) {
+                close(j > 0);
+                continue;
+            }
+            const bool to_end = j + take == g.chunks;
+            const uint64_t nb = to_end ? (take - 1) * W + mlst_chunk_len(g, n, W, k, g.chunks - 1) : take * W;
+            runs->push_back(MlstChunkRun{cu, ho[rec], n, W, j, bu, rec, 0});
+            cu += take;
+            bu += nb;
+            j += take;
+        }
+    }
+    if (cu) close(false);
+}
+
+int mlst_contigs_run(xs_bank* const* loci, uint32_t n_loci, const uint64_t* width, const xs_mlst_chunk_rule_t& rule,
+                     const Inputs& all, const uint64_t* ho, uint32_t step, uint64_t workspace_bytes,
+                     const MlstTypeOut& out) {
+    xs_bank* b0 = loci[0];
+    const hipStream_t s = b0->stream;
+    const uint64_t n = all.n, L = n_loci;
+    const uint32_t k = b0->k;
+    uint64_t dmax = 1;
+    for (uint32_t l = 0; l < n_loci; ++l) dmax = std::max(dmax, loci[l]->D);
+    const uint64_t ws = workspace_bytes ? workspace_bytes : kMlstTypeWs;
+    const uint64_t row_cap = std::min<uint64_t>(std::max<uint64_t>(1, ws / (dmax * 4)), (1ull << 31) - 1);
+
+    // the records by kind: the long ones, and the runs of consecutive short ones
+    std::vector<uint64_t> longs;
+    std::vector<std::pair<uint64_t, uint64_t>> short_runs;
+    uint64_t n_short = 0, short_bytes = 0;
+    for (uint64_t r = 0, run = 0; r <= n; ++r) {
+        const bool is_long = r < n && ho[r + 1] - ho[r] >= rule.long_len;
+        if (r == n || is_long) {
+            if (r > run) {
+                short_runs.emplace_back(run, r);
+                n_short += r - run;
+                short_bytes += ho[r] - ho[run];
+            }
+            run = r + 1;
+            if (is_long) longs.push_back(r);
+        }
+    }
+    const bool compact = short_runs.size() > kMaxShortRuns;
+
+    // every locus' ranges and runs, in one pinned array sent once
+    std::vector<MlstChunkRun> runs;
+    std::vector<ChunkRange> ranges;
+    std::vector<size_t> locus_end(n_loci);
+    for (uint32_t l = 0; l < n_loci; ++l) {
+        cut_chunk_ranges(longs, ho, width[l], k, rule, row_cap, std::max<uint64_t>(ws, 1), &runs, &ranges);
+        locus_end[l] = ranges.size();
+    }
+    uint64_t max_nc = 0, max_bytes = 0, max_runs = 0;
+    for (const ChunkRange& g : ranges) {
+        max_nc = std::max(max_nc, g.nc);
+        max_bytes = std::max(max_bytes, g.bytes);
+        max_runs = std::max(max_runs, g.n_runs);
+    }
+
+    if (int rc = ws_enter(b0, s)) return rc;
+    const uint64_t short_per = std::min(row_cap, std::max<uint64_t>(n_short, 1));
+    if (int rc = b0->hits.ensure(std::max(short_per, max_nc) * dmax * 4)) return rc;
+    if (int rc = b0->best.ensure(n * L * 4 * 3)) return rc;
+    uint32_t* d_rows = b0->hits.as<uint32_t>();
+    uint32_t* d_top = b0->best.as<uint32_t>();
+    uint32_t* d_score = d_top + n * L;
+    uint32_t* d_tied = out.n_tied ? d_score + n * L : nullptr;
+    uint64_t* d_nk = nullptr;
+    if (out.num_kmers) {  // of every record, long ones too, from the lengths alone
+        if (int rc = b0->nk.ensure(n * 8)) return rc;
+        if (int rc = b0->nseg.ensure((n + 1) * 8)) return rc;
+        d_nk = b0->nk.as<uint64_t>();
+        HIPCHK(launch_units(all.offs, n, k, step, d_nk, b0->nseg.as<uint64_t>(), s));
+    }
+
+    // ---- short records
+    if (!compact) {
+        for (const auto& run : short_runs) {
+            const uint64_t o = run.first * L;
+            if (int rc = mlst_type_span(loci, n_loci, all, ho, run.first, run.second - run.first, row_cap, step, d_rows,
+                                        d_top + o, d_score + o, d_tied ? d_tied + o : nullptr, s))
+                return rc;
+        }
+    } else {
+        const uint64_t m = n_short;
+        if (m >= (1ull << 32)) return fail(XS_ERR_ARG, "at most 2^32-1 short records per call");
+        if (int rc = b0->mc_idx_h.ensure((m + 1) * 8 + m * 4)) return rc;
+        if (int rc = b0->mc_idx.ensure((m + 1) * 8 + m * 4)) return rc;
+        if (int rc = b0->mc_short.ensure(short_bytes + kPad)) return rc;
+        if (int rc = b0->mc_out.ensure(m * L * 4 * 3)) return rc;
+        uint64_t* co = static_cast<uint64_t*>(b0->mc_idx_h.p);  // the compacted reads' m + 1 offsets, then their indices
+        uint32_t* ci = reinterpret_cast<uint32_t*>(co + m + 1);
+        uint64_t j = 0, ob = 0;
+        for (const auto& run : short_runs)
+            for (uint64_t r = run.first; r < run.second; ++r, ++j) {
+                co[j] = ob;
+                ci[j] = (uint32_t)r;
+                ob += ho[r + 1] - ho[r];
+            }
+        co[m] = ob;
+        HIPCHK(hipMemcpyAsync(b0->mc_idx.p, co, (m + 1) * 8 + m * 4, hipMemcpyHostToDevice, s));
+        const uint64_t* d_co = b0->mc_idx.as<uint64_t>();
+        const uint32_t* d_ci = reinterpret_cast<const uint32_t*>(d_co + m + 1);
+        HIPCHK(launch_gather_reads(all.seqs, all.offs, d_ci, m, b0->mc_short.as<uint8_t>(), d_co, s));
+        HIPCHK(hipMemsetAsync(b0->mc_short.as<uint8_t>() + short_bytes, 0, kPad, s));
+        uint32_t* c_top = b0->mc_out.as<uint32_t>();
+        uint32_t* c_score = c_top + m * L;
+        uint32_t* c_tied = d_tied ? c_score + m * L : nullptr;
+        const Inputs shorts{b0->mc_short.as<uint8_t>(), short_bytes, d_co, m};
+        if (int rc = mlst_type_span(loci, n_loci, shorts, co, 0, m, row_cap, step, d_rows, c_top, c_score, c_tied, s))
+            return rc;
+        HIPCHK(launch_mlst_scatter_rows(d_ci, m, L, c_top, c_score, c_tied, d_top, d_score, d_tied, s));
+    }
+
+    // ---- long records
+    if (!ranges.empty()) {
+        const size_t run_bytes = runs.size() * sizeof(MlstChunkRun);
+        if (int rc = b0->mc_runs_h.ensure(run_bytes)) return rc;
+        if (int rc = b0->mc_runs.ensure(run_bytes)) return rc;
+        if (int rc = b0->mc_text.ensure(max_bytes + kPad)) return rc;
+        if (int rc = b0->mc_offs.ensure((max_nc + 1) * 8)) return rc;
+        if (int rc = b0->mc_sum.ensure(max_runs * dmax * 8)) return rc;
+        if (int rc = b0->mc_key.ensure(max_runs * dmax * 8)) return rc;
+        memcpy(b0->mc_runs_h.p, runs.data(), run_bytes);
+        HIPCHK(hipMemcpyAsync(b0->mc_runs.p, b0->mc_runs_h.p, run_bytes, hipMemcpyHostToDevice, s));
+        uint8_t* text = b0->mc_text.as<uint8_t>();
+        uint64_t* coffs = b0->mc_offs.as<uint64_t>();
+        auto* sum = b0->mc_sum.as<unsigned long long>();
+        auto* key = b0->mc_key.as<unsigned long long>();
+        size_t gi = 0;
+        for (uint32_t l = 0; l < n_loci; ++l) {
+            const uint64_t D = loci[l]->D;
+            for (; gi < locus_end[l]; ++gi) {
+                const ChunkRange& g = ranges[gi];
+                const MlstChunkRun* d_runs = b0->mc_runs.as<MlstChunkRun>() + g.run0;
+                const uint64_t keep = g.carry_in ? 1 : 0;  // slot 0 holds the record the last range left unfinished
+                if (g.n_runs > keep) {
+                    HIPCHK(hipMemsetAsync(sum + keep * D, 0, (g.n_runs - keep) * D * 8, s));
+                    HIPCHK(hipMemsetAsync(key + keep * D, 0xFF, (g.n_runs - keep) * D * 8, s));
+                }
+                HIPCHK(launch_mlst_split(all.seqs, d_runs, g.n_runs, g.nc, k, text, coffs, s));
+                const Inputs in{text, g.bytes, coffs, g.nc, g.bytes};
+                if (int rc = run_query(loci[l], in, step, d_rows, nullptr, nullptr, s)) return rc;
+                HIPCHK(launch_mlst_chunk_acc(d_rows, g.nc, D, &d_runs->row0, kMlstRunWords, g.n_runs, rule.threshold,
+                                             g.chunk_base, sum, key, s));
+                const uint64_t done = g.n_runs - (g.carry_out ? 1 : 0);
+                HIPCHK(launch_mlst_owner_top(sum, key, done, D, &d_runs->rec, kMlstRunWords, d_top + l, d_score + l,
+                                             d_tied ? d_tied + l : nullptr, L, s));
+                if (g.carry_out && done > 0) {
+                    HIPCHK(hipMemcpyAsync(sum, sum + done * D, D * 8, hipMemcpyDeviceToDevice, s));
+                    HIPCHK(hipMemcpyAsync(key, key + done * D, D * 8, hipMemcpyDeviceToDevice, s));
+                }
+            }
+        }
+    }
+    if (int rc = ws_leave(b0, s)) return rc;
+    const D2hPart parts[4] = {{out.top, d_top, n * L * 4},
+                              {out.top_score, d_score, n * L * 4},
+                              {out.n_tied, d_tied, d_tied ? n * L * 4 : 0},
+                              {out.num_kmers, d_nk, d_nk ? n * 8 : 0}};
+    return d2h_parts(b0, parts, 4, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1101,6 +1347,131 @@ int xs_mlst_type_device(xs_bank* const* loci, uint32_t n_loci, const void* d_seq
         if (n == 0) return XS_OK;
         const Inputs in{static_cast<const uint8_t*>(d_seqs), seq_bytes, d_offsets, n};
         return mlst_type_run(loci, n_loci, in, nullptr, step, workspace_bytes, out);
+    });
+}
+
+int xs_mlst_type_contigs(xs_bank* const* loci, uint32_t n_loci, const uint64_t* locus_width,
+                         const xs_mlst_chunk_rule_t* rule, const char* seqs, const uint64_t* offsets, uint64_t n,
+                         uint32_t step, uint64_t workspace_bytes, uint32_t* top, uint32_t* top_score, uint32_t* n_tied,
+                         uint64_t* num_kmers_out) {
+    return xs::guard([&]() -> int {
+        const MlstTypeOut out{top, top_score, n_tied, num_kmers_out};
+        if (!offsets || (!seqs && n)) return fail(XS_ERR_ARG, "null argument");
+        xs_mlst_chunk_rule_t r;
+        if (int rc = mlst_contigs_check(loci, n_loci, locus_width, rule, offsets[n] - offsets[0], n, step, out, &r))
+            return rc;
+        LociLock lk(loci, n_loci);
+        HIPCHK(hipSetDevice(loci[0]->device));
+        if (n == 0) return XS_OK;
+        DrainStream drain{loci[0]->stream};
+        if (int rc = ws_enter(loci[0], loci[0]->stream)) return rc;
+        Inputs in;
+        if (int rc = upload_reads(loci[0], seqs, offsets, n, loci[0]->stream, &in)) return rc;
+        return mlst_contigs_run(loci, n_loci, locus_width, r, in, static_cast<const uint64_t*>(loci[0]->offs_h.p), step,
+                                workspace_bytes, out);
+    });
+}
+
+int xs_mlst_type_contigs_device(xs_bank* const* loci, uint32_t n_loci, const uint64_t* locus_width,
+                                const xs_mlst_chunk_rule_t* rule, const void* d_seqs, uint64_t seq_bytes,
+                                const uint64_t* d_offsets, const uint64_t* host_offsets, uint64_t n, uint32_t step,
+                                uint64_t workspace_bytes, uint32_t* top, uint32_t* top_score, uint32_t* n_tied,
+                                uint64_t* num_kmers_out) {
+    return xs::guard([&]() -> int {
+        const MlstTypeOut out{top, top_score, n_tied, num_kmers_out};
+        if (n && (!d_seqs || !d_offsets)) return fail(XS_ERR_ARG, "null argument");
+        xs_mlst_chunk_rule_t r;
+        if (int rc = mlst_contigs_check(loci, n_loci, locus_width, rule, seq_bytes, n, step, out, &r)) return rc;
+        LociLock lk(loci, n_loci);
+        HIPCHK(hipSetDevice(loci[0]->device));
+        if (n == 0) return XS_OK;
+        DrainStream drain{loci[0]->stream};
+        std::vector<uint64_t> copied;
+        if (!host_offsets) {  // the lengths decide the chunk geometry: one copy back
+            copied.resize(n + 1);
+            HIPCHK(hipMemcpy(copied.data(), d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost));
+            host_offsets = copied.data();
+        }
+        for (uint64_t i = 0; i < n; ++i)
+            if (host_offsets[i + 1] < host_offsets[i]) return bad_offsets();
+        if (host_offsets[0] != 0 || host_offsets[n] > seq_bytes)
+            return fail(XS_ERR_ARG, "offsets must start at 0 and end within seq_bytes");
+        const Inputs in{static_cast<const uint8_t*>(d_seqs), seq_bytes, d_offsets, n};
+        return mlst_contigs_run(loci, n_loci, locus_width, r, in, host_offsets, step, workspace_bytes, out);
+    });
+}
+
+int xs_mlst_split_size(const uint64_t* lengths, uint64_t n_long, uint64_t width, uint32_t k,
+                       const xs_mlst_chunk_rule_t* rule, uint64_t* n_chunks, uint64_t* chunk_bytes) {
+    return xs::guard([&]() -> int {
+        if ((!lengths && n_long) || !n_chunks || !chunk_bytes) return fail(XS_ERR_ARG, "null argument");
+        xs_mlst_chunk_rule_t r;
+        if (int rc = chunk_rule_check(rule, &r)) return rc;
+        if (k == 0 || width < k) return fail(XS_ERR_ARG, "width must be >= k >= 1");
+        if (r.long_len < k) return fail(XS_ERR_ARG, "long_len must be >= k = %u", k);
+        uint64_t c = 0, b = 0;
+        for (uint64_t i = 0; i < n_long; ++i) {
+            const MlstRecGeom g =
+                mlst_rec_geom(lengths[i], mlst_chunk_width(lengths[i], width, r.scale10_len, r.scale100_len), k);
+            c += g.chunks;
+            b += g.bytes;
+        }
+        *n_chunks = c;
+        *chunk_bytes = b;
+        return XS_OK;
+    });
+}
+
+int xs_mlst_split_device(const void* d_seqs, const uint64_t* d_offsets, const uint32_t* d_long_index, uint64_t n_long,
+                         uint64_t width, uint32_t k, const xs_mlst_chunk_rule_t* rule, void* d_chunk_seqs,
+                         uint64_t* d_chunk_offsets, uint64_t* d_owner_begin, void* stream) {
+    return xs::guard([&]() -> int {
+        if (!d_chunk_seqs || !d_chunk_offsets || !d_owner_begin || (n_long && (!d_seqs || !d_offsets || !d_long_index)))
+            return fail(XS_ERR_ARG, "null argument");
+        xs_mlst_chunk_rule_t r;
+        if (int rc = chunk_rule_check(rule, &r)) return rc;
+        if (k == 0 || width < k) return fail(XS_ERR_ARG, "width must be >= k >= 1");
+        if (r.long_len < k) return fail(XS_ERR_ARG, "long_len must be >= k = %u", k);
+        const hipStream_t s = static_cast<hipStream_t>(stream);
+        // the runs live for this call only: it returns once the chunks are written
+        DevBuf runs;
+        if (int rc = runs.ensure((n_long + 1) * sizeof(MlstChunkRun))) return rc;
+        HIPCHK(launch_mlst_runs(d_offsets, d_long_index, n_long, width, k, r.scale10_len, r.scale100_len,
+                                runs.as<MlstChunkRun>(), d_owner_begin, s));
+        uint64_t nc = 0;
+        HIPCHK(hipMemcpyAsync(&nc, d_owner_begin + n_long, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(launch_mlst_split(static_cast<const uint8_t*>(d_seqs), runs.as<MlstChunkRun>(), n_long, nc, k,
+                                 static_cast<uint8_t*>(d_chunk_seqs), d_chunk_offsets, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return XS_OK;
+    });
+}
+
+int xs_mlst_chunk_top_device(const uint32_t* d_hits, uint64_t n_chunks, uint64_t num_docs,
+                             const uint64_t* d_owner_begin, uint64_t n_owners, uint32_t threshold, uint32_t* d_top,
+                             uint32_t* d_top_score, uint32_t* d_n_tied, uint64_t out_stride, void* stream) {
+    return xs::guard([&]() -> int {
+        if ((n_owners && (!d_owner_begin || !d_top || !d_top_score)) || (n_chunks && !d_hits))
+            return fail(XS_ERR_ARG, "null argument");
+        if (num_docs == 0 || num_docs > 0xFFFFFFFFull) return fail(XS_ERR_ARG, "num_docs must be in 1 .. 2^32-1");
+        if (out_stride == 0) return fail(XS_ERR_ARG, "out_stride must be >= 1");
+        if (n_chunks >= (1ull << 32)) return fail(XS_ERR_ARG, "at most 2^32-1 chunks per call");
+        if (n_owners == 0) return XS_OK;
+        const hipStream_t s = static_cast<hipStream_t>(stream);
+        // the accumulators live for this call only: it returns once the outputs are written
+        DevBuf acc;
+        const uint64_t cells = n_owners * num_docs;
+        if (int rc = acc.ensure(cells * 16)) return rc;
+        auto* sum = acc.as<unsigned long long>();
+        auto* key = sum + cells;
+        HIPCHK(hipMemsetAsync(sum, 0, cells * 8, s));
+        HIPCHK(hipMemsetAsync(key, 0xFF, cells * 8, s));
+        HIPCHK(launch_mlst_chunk_acc(d_hits, n_chunks, num_docs, d_owner_begin, 1, n_owners, threshold, 0, sum, key, s));
+        HIPCHK(launch_mlst_owner_top(sum, key, n_owners, num_docs, nullptr, 0, d_top, d_top_score, d_n_tied, out_stride,
+                                     s));
+        HIPCHK(hipStreamSynchronize(s));
+        return XS_OK;
     });
 }
 

@@ -9,9 +9,9 @@ first result is the top allele (``:272-286``); longer ones are split by
 stably sorted by -score (``:248-256``).  What changes: every chunk of every
 record of a locus (and every short record) is probed in one batched GPU call
 (xs_mlst_query) instead of one COBS call per chunk, and the > 50 chunk sums
-are made on the device.  ``predict_columnar`` types many reads without the
-per-record dictionaries: all loci in one call (xs_mlst_type), each hit row
-reduced on the device to its top allele.  The PubMLST strain-type POST (``:295-302``) is network I/O and is
+are made on the device.  ``predict_columnar`` types many records without the
+per-record dictionaries: all loci in one call (xs_mlst_type_contigs), each hit
+row, and each contig's chunk sums, reduced on the device to the top allele.  The PubMLST strain-type POST (``:295-302``) is network I/O and is
 delegated to ``strain_type_resolver``.
 """
 from __future__ import annotations
@@ -22,8 +22,8 @@ from pathlib import Path
 
 import numpy as np
 
-from ._lib import XS_BANK_COBS_COMPACT, XS_MLST_NONE
-from .bank import Bank, cobs_signature_size, mlst_type
+from ._lib import XS_BANK_COBS_COMPACT
+from .bank import Bank, cobs_signature_size, mlst_type_contigs
 from .file_io import (check_input_path, file_reader_device, get_record_iterator, is_record, read_batches,
                       seq_text)
 from .packing import PackedIds, pack_sequences
@@ -295,47 +295,27 @@ class ProbabilisticFilterMlstSchemeModel(ProbabilisticFilterModel):
         return MlstResult(self.model_display_name, step, hits, None)
 
     # ------------------------------------------------------------ columnar typing
-    def _long_tops(self, texts: list[str], step: int):
-        """(top, score, n_tied) [len(texts), loci] of records of 10 kbp and more:
-        the existing per-locus chunk path (xs_mlst_query), whose small per-owner
-        sums are reduced here in ``_summed_counts`` order.  No passing chunk at a
-        locus: XS_MLST_NONE, 0, 0."""
-        L = len(self.indices)
-        top = np.full((len(texts), L), XS_MLST_NONE, dtype=np.uint32)
-        score = np.zeros((len(texts), L), dtype=np.uint64)
-        tied = np.zeros((len(texts), L), dtype=np.uint32)
-        for li, (bank, (_, rows_long)) in enumerate(zip(self.indices, self._locus_rows(texts, step))):
-            doc_of = {name: d for d, name in enumerate(bank.doc_names)}
-            for j in range(len(texts)):
-                counts = self._summed_counts(bank, rows_long[j])
-                if counts:
-                    first_key = next(iter(counts))
-                    top[j, li], score[j, li] = doc_of[first_key], counts[first_key]
-                    tied[j, li] = int((rows_long[j][0] == counts[first_key]).sum())
-        return top, score, tied
-
-    def _type_batch(self, reads, lengths: np.ndarray, text_of, step: int):
-        """One batch typed: every record through one xs_mlst_type call over all
-        loci, then the records of 10 kbp and more (``text_of(indices)`` gives
-        their texts) replaced by the chunk path's values."""
+    def _type_batch(self, reads, lengths: np.ndarray, step: int):
+        """One batch typed in one xs_mlst_type_contigs call over all loci: records
+        shorter than 10 kbp by their hit row's top allele, longer ones cut into
+        chunks, scored and reduced on the device (no chunk left above the
+        threshold at a locus: XS_MLST_NONE, 0, 0).  Nothing of the batch returns
+        to the host but the three columns."""
         if (lengths <= self.k).any():
             raise ValueError("Invalid sequence, must be longer than k")
-        top, score, tied, _ = mlst_type(self.indices, reads, step)
-        score = score.astype(np.uint64)
-        long_ = np.flatnonzero(lengths >= LONG_SEQUENCE)
-        if long_.size:
-            top[long_], score[long_], tied[long_] = self._long_tops(text_of(long_), step)
-        return top, score, tied
+        top, score, tied, _ = mlst_type_contigs(self.indices, reads, self.avg_locus_bp_size, step)
+        return top, score.astype(np.uint64), tied
 
     def predict_columnar(self, sequence_input, step: int = 1) -> MlstColumnarResult:
         """The typing as a MlstColumnarResult: per record and locus the top
         allele, its score and how many alleles share it, and per record the
         sufficiency flag, the numbers ``predict`` puts under "Strain type"
         (:272-303) without a dictionary of every allele per record.  Same inputs
-        and ValueErrors as ``predict``.  Records shorter than 10 kbp go through
-        one xs_mlst_type call over all loci (reads uploaded once, rows reduced on
-        the device); a path is read batch by batch, by the device reader where
-        the species model's file path would use it."""
+        and ValueErrors as ``predict``.  Each batch, short reads and contigs
+        alike, goes through one xs_mlst_type_contigs call over all loci (reads
+        uploaded once; rows, chunks and chunk sums reduced on the device); a path
+        is read batch by batch, by the device reader where the species model's
+        file path would use it."""
         if step < 1:
             raise ValueError("step must be >= 1")
         if isinstance(sequence_input, Path):
@@ -348,12 +328,7 @@ class ProbabilisticFilterMlstSchemeModel(ProbabilisticFilterModel):
             dev = file_reader_device(self.indices[0])
             ids, parts = [], []
             for batch in read_batches(sequence_input, device=dev):
-                def text_of(idx, batch=batch):  # the few long records' texts (a device batch: copied back)
-                    packed = batch.to_host() if dev is not None else batch.packed
-                    o = packed.offsets
-                    return [packed.buf[int(o[i]):int(o[i + 1])].tobytes().decode("ascii") for i in idx]
-                parts.append(self._type_batch(batch if dev is not None else batch.packed, batch.lengths(),
-                                              text_of, step))
+                parts.append(self._type_batch(batch if dev is not None else batch.packed, batch.lengths(), step))
                 ids.append(batch.ids_packed())
             ids = PackedIds.concat(ids) if ids else []
         else:
@@ -378,8 +353,7 @@ class ProbabilisticFilterMlstSchemeModel(ProbabilisticFilterModel):
             if not self.indices:
                 raise ValueError("The model has not been trained yet")
             ids = [r.id for r in records]
-            parts = [self._type_batch(pack_sequences(texts), lengths, lambda idx: [texts[i] for i in idx], step)] \
-                if texts else []
+            parts = [self._type_batch(pack_sequences(texts), lengths, step)] if texts else []
         L = len(self.indices)
         cols = [np.concatenate([p[c] for p in parts]) if parts else np.zeros((0, L), dt)
                 for c, dt in enumerate((np.uint32, np.uint64, np.uint32))]
