@@ -199,3 +199,73 @@ def test_saved_files_follow_the_spec_layouts(tmp_path, oracle_mod):
     bb.close()
     bb2.close()
     assert XS_BANK_COBS_CLASSIC == 0
+
+
+def test_host_build_through_the_upload_ring_equals_device_build():
+    """xs_bank_build stages host reads through the pinned H2D ring (two 32 MiB slots): a batch of
+    two full slots, a reused slot and a partial last piece, with one record longer than a slot,
+    must give the bank that xs_bank_build_device gives from the same bytes already in HBM.
+
+    The bank is sized by the project's formula (cobs_signature_size) for its largest document at
+    h = 3 and a false-positive rate of 0.3 per k-mer and document, so it is far from saturated:
+    reads cut from the input score every one of their k-mers for their document, and an
+    unrelated random read of 130 k-mers scores all of them with probability 0.3^130."""
+    torch = pytest.importorskip("torch")
+    from xspect2_amd.bank import Bank, cobs_signature_size
+    from xspect2_amd.packing import PackedReads
+
+    k, h, L = 21, 3, 150
+    slot = 32 << 20
+    # one record longer than a slot (it spans the first seam), one across the second seam, an
+    # empty one, one shorter than k, and a tail: 2 slots + 1.4 MB
+    lens = np.array([34_000_000, 17_000_000, 17_000_000, 0, 20, 500_003], dtype=np.uint64)
+    docs = np.array([0, 1, 2, 3, 3, 3], dtype=np.uint32)
+    offs = np.zeros(lens.size + 1, dtype=np.uint64)
+    np.cumsum(lens, out=offs[1:])
+    total = int(offs[-1])
+    assert 2 * slot < total < 3 * slot and int(offs[1]) > slot and int(offs[2]) < 2 * slot < int(offs[3])
+    rng = np.random.default_rng(3264)
+    buf = ACGT[rng.integers(0, 4, total + 1, dtype=np.uint8)]
+    D = 4
+    sig = cobs_signature_size(int(lens.max()) - k + 1, h, 0.3)
+
+    # reads cut from the input: around both ring seams, at every record's ends, and at random
+    starts = []
+    for seam in (slot, 2 * slot):
+        for s in range(seam - L, seam + 1, 10):
+            starts.append(s)
+    for r in (0, 1, 2, 5):
+        starts += [int(offs[r]), int(offs[r + 1]) - L]
+        starts += [int(x) for x in rng.integers(int(offs[r]), int(offs[r + 1]) - L + 1, 240)]
+    starts = np.array(starts)
+    want_doc = docs[np.searchsorted(offs, starts, side="right") - 1]
+    assert (np.searchsorted(offs, starts + L - 1, side="right") - 1 == np.searchsorted(offs, starts, side="right") - 1).all()
+    inserted = [buf[s:s + L].tobytes() for s in starts]
+    unrelated = [ACGT[rng.integers(0, 4, L)].tobytes() for _ in range(1000)]
+    nk = L - k + 1
+
+    def rows(bank):
+        hi, ni = bank.query(inserted)
+        hu, nu = bank.query(unrelated)
+        assert (ni == nk).all() and (nu == nk).all()
+        return hi, hu
+
+    host = Bank.create_cobs(k, h, [sig], D, device=0)
+    host.build(PackedReads(buf, offs), docs)
+    host_in, host_un = rows(host)
+    host.close()
+
+    dev = torch.device("cuda", 0)
+    device = Bank.create_cobs(k, h, [sig], D, device=0)
+    d_buf = torch.from_numpy(buf).to(dev)
+    device.build_device(d_buf, total, torch.from_numpy(offs.astype(np.int64)).to(dev), lens.size,
+                        torch.from_numpy(docs.astype(np.int32)).to(dev),
+                        stream=torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize(dev)
+    dev_in, dev_un = rows(device)
+    device.close()
+
+    assert len(inserted) >= 1000
+    assert np.array_equal(host_in, dev_in) and np.array_equal(host_un, dev_un)
+    assert (host_in[np.arange(len(inserted)), want_doc] == nk).all()  # no false negatives: every byte arrived
+    assert int(host_un.max()) < nk                                   # and the image is not all ones

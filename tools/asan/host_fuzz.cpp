@@ -3,9 +3,11 @@
 // libxspect_hip.so: randomised well-formed and malformed inputs, every batch
 // size from one byte up, 1..8 parser threads.  Functional equality with
 // Biopython / json.dumps is tested in tests/test_fastx.py and
-// tests/test_json_writer.py; this driver looks for memory errors only.
+// tests/test_json_writer.py; this driver looks for memory errors only.  It also drives the host's plan
+// of a contig typing call (xs_mlst_plan.h) over randomised record lengths and checks its invariants.
 //   make -C tools/asan run
 #include <atomic>
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -19,10 +21,15 @@
 
 #include "../../include/xspect_hip.h"
 #include "../../xspect2_amd/csrc/xs_internal.h"
+#include "../../xspect2_amd/csrc/xs_mlst_plan.h"
 
 namespace xs {
 int set_error(int code, const char* msg) {  // the library's version lives in xs_api.cpp (GPU side)
     (void)msg;
+    return code;
+}
+int fail(int code, const char* fmt, ...) {  // likewise
+    (void)fmt;
     return code;
 }
 // likewise (xs_api.cpp pins host memory; no GPU here, so plain host memory)
@@ -107,6 +114,111 @@ static void write_file(const std::string& path, const std::string& text) {
     FILE* f = fopen(path.c_str(), "wb");
     fwrite(text.data(), 1, text.size(), f);
     fclose(f);
+}
+
+// The plan of a contig typing call: record lengths around every threshold of the chunk rule and
+// around the chunk widths, runs of short records between long ones, zero-length records; row and
+// text caps from 1 up.  Returns the broken invariants; *plans counts the (lengths, width, caps) tried.
+static int fuzz_mlst_plan(int* plans) {
+    int bad = 0;
+    auto expect = [&](bool ok, const char* what) {
+        if (!ok && bad++ < 10) fprintf(stderr, "mlst plan: %s\n", what);
+    };
+    for (int trial = 0; trial < 300; ++trial) {
+        const uint32_t k = (uint32_t[]){1, 7, 21, 31}[rng() % 4];
+        xs_mlst_chunk_rule_t rule = xs::kReferenceRule;
+        rule.long_len = k + rng() % 300;
+        rule.scale10_len = rule.long_len + rng() % 1700;
+        rule.scale100_len = rule.scale10_len + rng() % 4000;
+        const uint64_t widths[3] = {k + rng() % 3, 2 * k + rng() % 100, 100 + rng() % 400};
+        std::vector<uint64_t> special{0, k - 1, k, k + 1, rule.long_len - 1, rule.long_len, rule.long_len + 1,
+                                      rule.scale10_len - 1, rule.scale10_len, rule.scale10_len + 1,
+                                      rule.scale100_len - 1, rule.scale100_len, rule.scale100_len + 1};
+        for (uint64_t w : widths)
+            for (uint64_t W : {w, 10 * w, 100 * w})
+                for (uint64_t n : {W - 1, W, W + 1, W + k - 2, W + k - 1, W + k, 2 * W, 2 * W - k + 1, 2 * W - k + 2})
+                    special.push_back(n);
+        // offsets: long records apart, in clusters, and between runs of short ones
+        std::vector<uint64_t> ho{0};
+        const int recs = (int)(rng() % 40);
+        for (int r = 0; r < recs; ++r) {
+            uint64_t len;
+            switch (rng() % 4) {
+                case 0: len = special[rng() % special.size()]; break;
+                case 1: len = rng() % (rule.long_len + 1); break;  // mostly short
+                case 2: len = rng() % (3 * rule.scale100_len + 1); break;
+                default: len = 0;
+            }
+            ho.push_back(ho.back() + len);
+        }
+        const uint64_t n = ho.size() - 1;
+        const xs::RecordKinds kinds = xs::classify_records(ho.data(), n, rule.long_len);
+        {  // the long records and the short runs partition the records in order
+            std::vector<int> seen(n, 0);
+            uint64_t ns = 0, sb = 0;
+            for (uint64_t r : kinds.longs) {
+                expect(r < n && ho[r + 1] - ho[r] >= rule.long_len, "a long record is short");
+                if (r < n) ++seen[r];
+            }
+            for (size_t i = 0; i < kinds.short_runs.size(); ++i) {
+                const auto run = kinds.short_runs[i];
+                expect(run.first < run.second && run.second <= n, "an empty or overlong short run");
+                expect(i == 0 || kinds.short_runs[i - 1].second < run.first, "short runs touch or overlap");
+                for (uint64_t r = run.first; r < run.second && r < n; ++r) {
+                    expect(ho[r + 1] - ho[r] < rule.long_len, "a short record is long");
+                    ++seen[r];
+                    ++ns;
+                    sb += ho[r + 1] - ho[r];
+                }
+            }
+            for (int c : seen) expect(c == 1, "a record is in no kind or in two");
+            expect(ns == kinds.n_short && sb == kinds.short_bytes, "short totals");
+        }
+        const uint64_t caps[][2] = {{1, 1}, {1, 1ull << 32}, {(1ull << 31) - 1, 1}, {2, 3}, {3, widths[2]},
+                                    {1 + rng() % 50, 1 + rng() % 20000}, {(1ull << 31) - 1, 4ull << 30}};
+        for (const auto& cap : caps) {
+            const uint64_t row_cap = cap[0], text_cap = cap[1];
+            std::vector<xs::MlstChunkRun> runs;
+            std::vector<xs::ChunkRange> ranges;
+            size_t first = 0;
+            for (uint64_t w : widths) {  // locus after locus into the same arrays, as a call does
+                xs::cut_chunk_ranges(kinds.longs, ho.data(), w, k, rule, row_cap, text_cap, &runs, &ranges);
+                ++*plans;
+                uint64_t want = 0;  // 1. the closed form xs_mlst_split_size returns
+                for (uint64_t r : kinds.longs) {
+                    const uint64_t len = ho[r + 1] - ho[r];
+                    want += xs::mlst_rec_geom(len, xs::mlst_chunk_width(len, w, rule.scale10_len, rule.scale100_len), k)
+                                .chunks;
+                }
+                uint64_t got = 0;
+                for (size_t i = first; i < ranges.size(); ++i) {
+                    const xs::ChunkRange& g = ranges[i];
+                    expect(g.chunk_base == got, "chunk_base is not the running sum");                       // 5.
+                    got += g.nc;
+                    expect(g.nc >= 1 && g.nc <= row_cap, "a range's chunks outside 1 .. row_cap");          // 2.
+                    expect(g.bytes <= text_cap || g.nc == 1, "a range of several chunks over text_cap");
+                    expect(g.n_runs >= 1 && g.run0 + g.n_runs < runs.size(), "a range's runs out of the array");
+                    if (g.run0 + g.n_runs >= runs.size()) continue;
+                    const xs::MlstChunkRun* rr = runs.data() + g.run0;
+                    expect(rr[0].row0 == 0 && rr[0].out == 0, "a range's first run does not start at 0");   // 3.
+                    for (uint64_t j = 0; j < g.n_runs; ++j) {
+                        expect(rr[j + 1].row0 > rr[j].row0 && rr[j + 1].out > rr[j].out, "row0 / byte0 not increasing");
+                        const xs::MlstRecGeom geom = xs::mlst_rec_geom(rr[j].n, rr[j].W, k);
+                        expect(rr[j].j0 + (rr[j + 1].row0 - rr[j].row0) <= geom.chunks, "a run past its record's chunks");
+                        const uint64_t rec = rr[j].rec;
+                        expect(rr[j].src == ho[rec] && rr[j].n == ho[rec + 1] - ho[rec], "a run's record");
+                    }
+                    expect(rr[g.n_runs].row0 == g.nc && rr[g.n_runs].out == g.bytes, "the sentinel's totals");
+                    expect(g.carry_in == (i > first && ranges[i - 1].carry_out), "carry_in is not the last carry_out");
+                    expect(g.carry_in == (rr[0].j0 > 0), "carry_in and the first run's j0 disagree");
+                    if (i + 1 == ranges.size()) expect(!g.carry_out, "the last range carries out");
+                }
+                expect(got == want, "chunks over the ranges differ from the closed form");
+                first = ranges.size();
+            }
+        }
+    }
+    return bad;
 }
 
 int main() {
@@ -294,9 +406,11 @@ int main() {
         const bool want = std::set<std::string>(ids.begin(), ids.end()).size() != n;
         if (dup != (want ? 1 : 0)) ++unexpected;
     }
-    printf("host sanitizer run: %d input files x 15 reader configurations + 12 byte-range parts, 20 JSON matrices, "
+    int plans = 0;
+    unexpected += fuzz_mlst_plan(&plans);
+    printf("host sanitizer run: %d MLST contig plans; %d input files x 15 reader configurations + 12 byte-range parts, 20 JSON matrices, "
            "20 id-key batches + a threaded one, 6 member masks, 6 threaded repeat checks, 1800 worker-pool jobs from 6 threads (nested, throwing); %d clean error returns, "
            "%d unexpected results\n",
-           files, errors, unexpected);
+           plans, files, errors, unexpected);
     return unexpected ? 1 : 0;
 }

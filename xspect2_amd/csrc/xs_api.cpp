@@ -1,5 +1,6 @@
-// xs_api.cpp — the C ABI (include/xspect_hip.h) beside bank files (xs_bank_io.cpp) and queries (xs_query.cpp):
-// errors, pinned host memory, device copies, handle information, profiling and options, handle teardown.
+// xs_api.cpp — the C ABI (include/xspect_hip.h) beside bank files (xs_bank_io.cpp), queries (xs_query.cpp) and
+// MLST (xs_mlst.cpp): errors, pinned host memory, device copies, handle information, profiling and options,
+// handle teardown.
 #include <sys/mman.h>
 
 #include <cstdarg>

@@ -1,5 +1,5 @@
-// xs_hitsink.h — hit rows back to a host array, behind the probe.  Included by
-// xs_query.cpp only.
+// xs_hitsink.h — hit rows back to a host array, behind the probe, and the host's own passes over
+// hit rows.  Included by xs_query.cpp only.
 #pragma once
 #include <sys/mman.h>
 
@@ -59,6 +59,26 @@ inline void narrow_rows(void* dst, int hit_bytes, const uint32_t* src, size_t n)
         for (size_t i = 0; i < n; ++i) static_cast<uint16_t*>(dst)[i] = (uint16_t)src[i];
     else
         for (size_t i = 0; i < n; ++i) static_cast<uint8_t*>(dst)[i] = (uint8_t)src[i];
+}
+
+// best_doc_kernel's rule on host rows (a small call's): per row of `cols` counts the document holding the
+// unique maximum, else kBestAmbiguous; best_hits (may be null) takes the maximum.
+inline void best_rows(const uint32_t* rows, uint64_t n, uint64_t cols, uint32_t* best_doc, uint32_t* best_hits) {
+    for (uint64_t r = 0; r < n; ++r) {
+        const uint32_t* row = rows + r * cols;
+        uint32_t m = 0, arg = 0, cnt = 0;
+        for (uint64_t c = 0; c < cols; ++c) {
+            if (cnt == 0 || row[c] > m) {
+                m = row[c];
+                arg = (uint32_t)c;
+                cnt = 1;
+            } else if (row[c] == m) {
+                ++cnt;
+            }
+        }
+        best_doc[r] = cnt == 1 ? arg : kBestAmbiguous;
+        if (best_hits) best_hits[r] = m;
+    }
 }
 
 // Narrowest transport width (bytes) of hit counts up to max_count, at most `out`.

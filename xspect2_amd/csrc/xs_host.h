@@ -1,4 +1,4 @@
-// xs_host.h — what xs_api.cpp, xs_bank_io.cpp and xs_query.cpp share: error reporting, the device
+// xs_host.h — what xs_api.cpp, xs_bank_io.cpp, xs_query.cpp and xs_mlst.cpp share: error reporting, the device
 // and pinned buffers, the bank handle and its workspace ordering.  Host only: never included
 // from a .hip file, and not part of the public ABI.
 #pragma once
@@ -13,9 +13,6 @@
 #include "xs_internal.h"
 
 namespace xs {
-
-// Set the thread-local message xs_last_error() returns (printf style); returns `code`.
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 #define HIPCHK(expr)                                                                           \
     do {                                                                                       \
@@ -155,15 +152,16 @@ struct xs_bank {
     int last_path = XS_PATH_GATHER;
     const char* last_kernel = "";    // name of the probe kernel the last query launched (a string literal)
     xs::ProbeOptions opt;           // path selection (xs_bank_set_probe_options)
-    xs::PinnedBuf stage[3];         // D2H staging ring for large host outputs (d2h_pageable: 2, HitSink: 3)
+    xs::PinnedBuf stage[3];         // D2H staging ring for large host outputs (d2h_parts: 2, HitSink: 3)
     hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr};
     xs::PinnedBuf hstage[2];        // H2D staging ring for host read batches
     xs::PinnedBuf small_h;          // small host calls: the whole request and its results (query_small)
     xs::PinnedBuf cut_ofs;          // device-read batches: read offsets at the chunk cuts
     xs::PinnedBuf offs_h;           // host batches: the read offsets rebased to 0, for their H2D copy
     xs::DevBuf small_d;
-    // MLST typing of contigs (mlst_contigs_run): a range's chunk texts, their offsets and accumulators, the call's
-    // chunk runs, and for a batch of many short runs the compacted short reads with their index and outputs
+    // MLST typing of contigs (mlst_contigs_run in xs_mlst.cpp): a range's chunk texts, their offsets and
+    // accumulators, the call's chunk runs, and for a batch of many short runs the compacted short reads with
+    // their index and outputs
     xs::DevBuf mc_text, mc_offs, mc_sum, mc_key, mc_runs, mc_short, mc_idx, mc_out;
     xs::PinnedBuf mc_runs_h, mc_idx_h;
     hipEvent_t hstage_ev[2] = {nullptr, nullptr};

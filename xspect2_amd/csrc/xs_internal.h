@@ -76,6 +76,11 @@ struct ReadView {
 };
 
 // ---- launchers (xs_kernels.hip) -------------------------------------------
+// k-mers sampled every `step` positions from a read of `len` bytes: units_kernel's formula, and the
+// host's wherever it needs the count without the device.
+__host__ __device__ inline uint64_t sampled_kmers(uint64_t len, uint32_t k, uint32_t step) {
+    return len >= k ? (len - k) / step + 1 : 0;
+}
 hipError_t launch_units(const uint64_t* offs, uint64_t n, uint32_t k, uint32_t step,
                         uint64_t* nk_out, uint64_t* nseg, hipStream_t s);
 size_t scan_temp_bytes(uint64_t n);
@@ -371,6 +376,8 @@ hipError_t launch_max_u64(void* temp, size_t temp_bytes, const uint64_t* in, uin
 
 // Set the thread-local message xs_last_error() returns; returns `code`.
 int set_error(int code, const char* msg);
+// The same, printf style.
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // Page-locked host memory for DMA staging and callers' outputs.  Requests of
 // 2 MiB and more are anonymous mappings backed by 2 MiB pages, faulted by up
