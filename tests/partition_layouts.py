@@ -1,0 +1,313 @@
+"""Read layouts that put read boundaries on the partitioned probes' edges.
+
+Helper of tests/test_partition_layouts.py (CPU) and
+tests/test_gpu_partitioned_edges.py (GPU); it needs no GPU and no library.
+
+The partitioned probes (xs_probe_cobspart.hip, xs_probe_bloompart.hip) give
+every sampled k-mer of a call a global id and work on bucket blocks of T
+consecutive ids (T = kCobsCK for COBS, kPartKmers for rbloom).  Which code a
+block runs depends on the reads it touches:
+
+    blk_read[b] = the read holding k-mer b*T
+    lo = blk_read[B]
+    hi = blk_read[B+1] if (B+1)*T < Nk else n-1
+
+`hi - lo + 1` against cnt_reads (LDS counters or global atomics in the COBS
+resolve pass), `hi - lo + 2` against kStageReads (read offsets staged in LDS
+or a global binary search per k-mer in both bucket passes), and whether a
+read's k-mers lie in one block (its row stored) or two (zeroed beforehand,
+added atomically by each).  This module restates that rule in numpy, reads
+the constants from the shipped sources (a change of block size moves the
+layouts with it), and names layouts, lists of per-read k-mer counts, built
+to land on each of those edges.
+"""
+from __future__ import annotations
+
+import re
+from pathlib import Path
+
+import numpy as np
+
+CSRC = Path(__file__).resolve().parents[1] / "xspect2_amd" / "csrc"
+
+
+# ---------------------------------------------------------------- constants
+def _src(name: str) -> str:
+    return (CSRC / name).read_text()
+
+
+def _const(file: str, name: str) -> int:
+    """`constexpr <type> name = <int>[u] [<< <int>];` of a shipped source."""
+    m = re.search(r"constexpr\s+\w+\s+" + name + r"\s*=\s*(\d+)u?(?:\s*<<\s*(\d+))?\s*;", _src(file))
+    assert m, f"{file}: constant {name} not found"
+    return int(m.group(1)) << int(m.group(2) or 0)
+
+
+def _cnt_reads_div() -> int:
+    m = re.search(r"cnt_reads\(\)\s*\{\s*return\s+CK\s*/\s*(\d+)\s*;", _src("xs_probe_cobspart.hip"))
+    assert m, "xs_probe_cobspart.hip: cnt_reads() is no longer CK / <int>"
+    return int(m.group(1))
+
+
+def _id_bits(ck: int) -> int:
+    m = re.search(r"id_bits\(\)\s*\{\s*return\s+([^;]*);", _src("xs_probe_cobspart.hip"))
+    assert m, "xs_probe_cobspart.hip: id_bits() not found"
+    expr = m.group(1)
+    pairs = re.findall(r"CK\s*==\s*(\d+)\s*\?\s*(\d+)", expr)
+    last = re.search(r":\s*(\d+)\s*$", expr)
+    assert pairs and last, f"xs_probe_cobspart.hip: id_bits() has another form: {expr!r}"
+    for size, bits in pairs:
+        if int(size) == ck:
+            return int(bits)
+    return int(last.group(1))
+
+
+def _emb_base() -> int:
+    m = re.search(r"emb_max_docs\(\)\s*\{\s*return\s+(\d+)\s*-\s*id_bits<CK>\(\)\s*;", _src("xs_probe_cobspart.hip"))
+    assert m, "xs_probe_cobspart.hip: emb_max_docs() is no longer <int> - id_bits<CK>()"
+    return int(m.group(1))
+
+
+COBS_CK = _const("xs_probe_cobspart.hip", "kCobsCK")       # k-mers per COBS bucket block
+PART_KMERS = _const("xs_internal.h", "kPartKmers")         # k-mers per rbloom bucket block
+STAGE_READS = _const("xs_part.h", "kStageReads")           # read offsets a bucket block stages in LDS
+SEG_KMERS = _const("xs_internal.h", "kSegKmers")           # k-mers per work unit (rbloom count pass)
+COBS_PAD_PARTS = _const("xs_internal.h", "kCobsPadParts")  # partitions up to which runs are padded
+PART_MAX = _const("xs_internal.h", "kPartMax")             # partitions of a plan at the most
+HOST_FIRST = _const("xs_query.cpp", "kHostFirst")          # sequence bytes of a host batch's first chunk
+CNT_DIV = _cnt_reads_div()
+ID_BITS = _id_bits(COBS_CK)
+EMB_MAX_DOCS = _emb_base() - ID_BITS                       # docs up to which the k-mer id rides in the row
+
+
+def cnt_reads(T: int) -> int:
+    """Reads per block with LDS counter rows (cnt_reads<CK>())."""
+    return T // CNT_DIV
+
+
+# ---------------------------------------------------------------- the rule
+def num_kmers(length: int, k: int, step: int) -> int:
+    return max(0, -(-(length - k + 1) // step))
+
+
+def kofs(counts) -> np.ndarray:
+    """First global k-mer id of every read, and the total (n + 1 entries)."""
+    out = np.zeros(len(counts) + 1, dtype=np.int64)
+    out[1:] = np.cumsum(np.asarray(counts, dtype=np.int64))
+    return out
+
+
+def blk_read(counts, T: int) -> np.ndarray:
+    """blk_read[b] = the read holding k-mer b*T, for every block with a k-mer."""
+    ko = kofs(counts)
+    nb = -(-int(ko[-1]) // T)
+    return np.searchsorted(ko, np.arange(nb, dtype=np.int64) * T, side="right") - 1
+
+
+def block_reads(counts, T: int, B: int) -> tuple[int, int]:
+    """(lo, hi) of bucket block B."""
+    br = blk_read(counts, T)
+    Nk = int(kofs(counts)[-1])
+    assert 0 <= B < len(br)
+    return int(br[B]), int(br[B + 1]) if (B + 1) * T < Nk else len(counts) - 1
+
+
+def block_table(counts, T: int) -> list[tuple[int, int]]:
+    return [block_reads(counts, T, B) for B in range(len(blk_read(counts, T)))]
+
+
+def read_classes(counts, T: int) -> list[str]:
+    """What the COBS resolve pass does with every read's hit row:
+    "empty" (no k-mers: zeroed), "stored" (all k-mers in one block whose reads
+    fit the LDS counters: stored once, never zeroed) or "added" (k-mers in two
+    blocks or more, or in a block with more reads than counter rows: zeroed,
+    then added atomically)."""
+    ko = kofs(counts)
+    tab = block_table(counts, T)
+    out = []
+    for r, c in enumerate(counts):
+        if c == 0:
+            out.append("empty")
+            continue
+        b0, b1 = int(ko[r]) // T, (int(ko[r + 1]) - 1) // T
+        lo, hi = tab[b0]
+        out.append("added" if b0 != b1 or hi - lo + 1 > cnt_reads(T) else "stored")
+    return out
+
+
+# ---------------------------------------------------------------- layouts
+def _split(T: int, reads: int) -> list[int]:
+    """`reads` k-mer-holding reads that fill one block exactly: equal counts,
+    the remainder added to the last ones (2048 over 254 reads: 252 x 8 + 2 x 16)."""
+    base = T // reads
+    assert base >= 1
+    out = [base] * reads
+    extra, i = T - base * reads, reads - 1
+    while extra > 0:
+        add = min(base, extra)
+        out[i] += add
+        extra -= add
+        i -= 1
+    assert sum(out) == T
+    return out
+
+
+def off_by_one_unit(T: int) -> list[int]:
+    """9 reads over 6 blocks: ends at T-1, T and T+1 past an edge, starts on an
+    edge and one k-mer after it, reads of 1 k-mer first and last in a block."""
+    return [T - 1,  # ends one k-mer before the edge
+            1,      # the block's last k-mer: ends on the edge
+            1,      # the next block's first k-mer: starts on the edge
+            T,      # starts one after an edge, ends one after the next
+            T - 1,  # starts one after an edge, ends on one
+            T + 1,  # starts on an edge, ends one after the next
+            T - 2,  # ends one before an edge
+            1,      # last k-mer of its block
+            T]      # one whole block
+
+
+def cnt_over_unit(T: int) -> list[int]:
+    """cnt_reads reads that fill one block: with the next block's first read one too many."""
+    return [T // cnt_reads(T)] * cnt_reads(T)
+
+
+def long_layout(T: int, blocks: int = 5) -> list[int]:
+    return [7, blocks * T + 3] + [0] * 40 + [T - 10]
+
+
+def _tails(T: int, target: int) -> list[int]:
+    body = [T // 2 + 7, 0, 0, 0, 0, 0, T, 0, T]
+    last = (target - sum(body)) % T or T
+    return [0, 0, 0] + body + [0, 0, last] + [0, 0, 0, 0]
+
+
+def layouts(T: int, word_phase: bool = False) -> dict[str, list[int]]:
+    """Every named layout for block size T: name -> k-mers per read (0 = an
+    empty or sub-k read).  `word_phase` adds the rbloom count pass's layout."""
+    cnt = cnt_reads(T)
+    fit = _split(T, cnt - 1)
+    out = {
+        "exact": [T] * 5,
+        "off_by_one": off_by_one_unit(T) + [5],
+        # block 1 holds cnt - 1 reads; with block 2's first read hi - lo + 1 == cnt
+        "cnt_fit": [T] + fit + [T // 2],
+        "cnt_over": [T] + cnt_over_unit(T) + [T // 2],
+        # the same edge with empty reads making up the count: one in the middle of
+        # the block, the others between its last k-mer and the next block's first read
+        "cnt_fit_empty": [T] + _with_empties(_split(T, cnt - 4), 3) + [T // 2],
+        "cnt_over_empty": [T] + _with_empties(_split(T, cnt - 4), 4) + [T // 2],
+        "stage_fit": [T] + _split(T, STAGE_READS - 2) + [T // 2],
+        "stage_over": [T] + _split(T, STAGE_READS - 1) + [T // 2],
+        "tails_0": _tails(T, 0),
+        "tails_1": _tails(T, 1),
+        "tails_m1": _tails(T, T - 1),
+        "long": long_layout(T),
+    }
+    if word_phase:
+        # first global k-mer ids 1, 31 and 32 (mod 32), each read longer than one work unit
+        out["word_phase"] = [1, SEG_KMERS + 62, SEG_KMERS + 33, SEG_KMERS + 44, 9]
+    return out
+
+
+def _with_empties(reads: list[int], empties: int) -> list[int]:
+    mid = len(reads) // 2
+    return reads[:mid] + [0] + reads[mid:] + [0] * (empties - 1)
+
+
+def repeated(T: int, kmers: int) -> list[int]:
+    """The off_by_one and cnt_over units, repeated to at least `kmers` k-mers, plus one block."""
+    unit = off_by_one_unit(T) + cnt_over_unit(T)
+    return unit * (-(-kmers // sum(unit))) + [T]
+
+
+# ---------------------------------------------------------------- reads
+def read_lengths(counts, k: int, step: int) -> list[int]:
+    """A read of c k-mers is k + (c-1)*step bytes plus 0..step-1 slack bytes
+    (num_kmers rounds up, so the slack must not add a k-mer); a read of 0
+    k-mers is empty or k-1 bytes long, in turn."""
+    out, z = [], 0
+    for i, c in enumerate(counts):
+        if c == 0:
+            out.append((0, k - 1)[z % 2])
+            z += 1
+        else:
+            out.append(k + (c - 1) * step + i % step)
+    assert [num_kmers(L, k, step) for L in out] == list(counts)
+    return out
+
+
+def make_reads(rng, counts, k: int, step: int) -> list[bytes]:
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    lens = read_lengths(counts, k, step)
+    buf = acgt[rng.integers(0, 4, sum(lens))].tobytes()
+    ofs = np.concatenate([[0], np.cumsum(lens)])
+    return [buf[int(ofs[i]):int(ofs[i + 1])] for i in range(len(lens))]
+
+
+# ---------------------------------------------------------------- plans
+def cobs_plan(sig: int, h: int, mode: int, kbound: int = 0, workspace_mib: int | None = None) -> dict:
+    """cobs_part_plan restated for modes 3 and 4: partition shift and count,
+    run padding, entries per block, and blocks per workspace range."""
+    assert mode in (3, 4)
+
+    def parts(s):
+        return (sig + (1 << s) - 1) >> s
+
+    shift = 10 if mode == 4 else 17
+    while mode != 4 and shift > 10 and parts(shift) < 64:
+        shift -= 1
+    while parts(shift) > PART_MAX:
+        shift += 1
+    P = parts(shift)
+    pad = 4 if P <= COBS_PAD_PARTS else 1
+    stride = (COBS_CK * h + (pad - 1) * P + 7) // 8 * 8
+    plan = {"shift": shift, "P": P, "pad": pad, "stride": stride, "last_rows": sig - ((P - 1) << shift)}
+    if workspace_mib is not None:
+        nblk = -(-kbound // COBS_CK)
+        plan["nblk"] = nblk
+        plan["rblk"] = max(1, min(nblk, (max(1, workspace_mib) << 20) // (stride * 20)))
+        plan["ranges"] = -(-nblk // plan["rblk"])
+    return plan
+
+
+def kbound(reads, step: int) -> int:
+    """The planner's bound on a call's k-mers: bytes / step + reads + 1."""
+    return sum(len(r) for r in reads) // step + len(reads) + 1
+
+
+def bloom_plan(nbytes: int) -> dict:
+    """bloom_part_plan restated for mode 3: partitions of 1024 bits, doubled while over kPartMax."""
+    mbits = nbytes * 8
+    shift = 10
+    while (mbits + (1 << shift) - 1) >> shift > PART_MAX:
+        shift += 1
+    P = (mbits + (1 << shift) - 1) >> shift
+    return {"shift": shift, "P": P, "last_bits": mbits - ((P - 1) << shift)}
+
+
+# ---------------------------------------------------------------- expectations
+def closed_form(counts, D: int, docs) -> np.ndarray:
+    """Hit matrix on an image whose every row has exactly the bits of `docs`."""
+    out = np.zeros((len(counts), D), dtype=np.uint32)
+    out[:, list(docs)] = np.asarray(counts, dtype=np.uint32)[:, None]
+    return out
+
+
+def misattribute_edge_kmers(counts, T: int) -> list[int]:
+    """What a probe would count that gave every block's first k-mer to the read
+    holding the k-mer before it."""
+    ko = kofs(counts)
+    out = list(counts)
+    for g in range(T, int(ko[-1]), T):
+        a = int(np.searchsorted(ko, g - 1, side="right")) - 1
+        b = int(np.searchsorted(ko, g, side="right")) - 1
+        if a != b:
+            out[a] += 1
+            out[b] -= 1
+    return out
+
+
+def double_added_rows(counts, T: int) -> list[int]:
+    """What a probe would count that stored an "added" read's row and then added
+    to it as well (or never zeroed it after an equal earlier call)."""
+    return [2 * c if cls == "added" else c for c, cls in zip(counts, read_classes(counts, T))]

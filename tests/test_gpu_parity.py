@@ -5,6 +5,8 @@ the bank images built on the device.  Inputs are seeded; edge cases follow
 what the reference's path meets: reads of length <= k (no k-mers), exactly
 k+1, non-ACGT bytes (N, IUPAC, lower case), long records split into several
 work units, sparse sampling steps, empty reads, D spanning 1..1000 docs.
+The partitioned probes' block, read and partition-count edges, placed on
+purpose, are in test_gpu_partitioned_edges.py.
 """
 from __future__ import annotations
 
