@@ -148,27 +148,34 @@ struct ProbeOptions {
     int small_calls = 1;                      // 0: small host calls take the regular pipeline
 };
 
-// Partitioned rbloom probe (xs_probe_bloompart.hip): k-mers per bucket block,
-// most hash functions it takes, most filter partitions.
-constexpr int kPartKmers = 1024;
-constexpr int kPartKMax = 8;
-constexpr uint32_t kPartMax = 1024;
-struct BloomPartPlan {
-    uint32_t shift;      // log2 filter bits per partition
-    uint32_t P;          // partitions
-    uint64_t tstride;    // bucket blocks (>= the call's k-mers / kPartKmers)
+// The partitioned probes (xs_probe_bloompart.hip, xs_probe_cobspart.hip; shared pieces in
+// xs_part.h).  What a plan asks of the workspace, and the workspace both launchers take:
+struct PartSizes {
     uint64_t kbound;     // upper bound of the call's sampled k-mers
-    size_t entry_bytes, tbl_bytes, miss_bytes, nkc_bytes, scan_bytes, aux_bytes;
+    size_t entry_bytes, tbl_bytes, nkc_bytes, scan_bytes, aux_bytes;
+    size_t miss_bytes = 0;  // rbloom only
 };
-struct BloomPartWs {
+struct PartWs {
     uint64_t* nkc;       // n+1 per-read k-mer counts
     uint64_t* kofs;      // n+1 exclusive scan: first k-mer id of each read
     void* scan_tmp;
     size_t scan_bytes;
-    uint64_t* entries;   // tstride regions of kPartKmers*K entries: u32 offsets, u16 k-mer ids, u8 miss flags
-    uint16_t* tbl;       // (P+1) x tstride partition starts per bucket block
-    uint32_t* miss;      // one bit per k-mer id: some filter bit was zero
-    uint32_t* aux;       // bucket block -> read holding its first k-mer (tstride+1), then per-partition queue counters
+    // rbloom: tstride regions of kPartKmers*K entries: u32 offsets, u16 k-mer ids, u8 miss flags
+    // COBS: a range's u32 entries (row in partition << id bits | k-mer in block), then their 16-B rows
+    void* entries;
+    uint16_t* tbl;       // (P+1) x blocks partition starts per bucket block, + block-major copy
+    uint32_t* miss;      // rbloom: one bit per k-mer id: some filter bit was zero (COBS: null)
+    uint32_t* aux;       // bucket block -> read holding its first k-mer (blocks+1), then per-partition queue counters
+};
+// Partitioned rbloom probe: k-mers per bucket block, most hash functions it
+// takes, most filter partitions.
+constexpr int kPartKmers = 1024;
+constexpr int kPartKMax = 8;
+constexpr uint32_t kPartMax = 1024;
+struct BloomPartPlan : PartSizes {
+    uint32_t shift;      // log2 filter bits per partition
+    uint32_t P;          // partitions
+    uint64_t tstride;    // bucket blocks (>= the call's k-mers / kPartKmers)
 };
 // False when the direct probe should run (small filter, K > kPartKMax, a
 // batch too large for the transient workspace, member-poor input -- the
@@ -176,43 +183,31 @@ struct BloomPartWs {
 // opt.bloom_part = 0).
 constexpr double kPartMinMembers = 0.24;  // measured crossover, profiles/r01_bloom_crossover.txt
 bool bloom_part_plan(const BloomView& bv, uint64_t n, uint64_t seq_bytes, uint32_t step, double member_frac,
-                     const ProbeOptions& opt, BloomPartPlan* plan);
+                     const ProbeOptions& opt, BloomPartPlan* plan = nullptr);  // null: the answer alone
 hipError_t launch_probe_bloom_part(const ReadView& rv, const BloomView& bv, const BloomPartPlan& plan,
-                                   const BloomPartWs& ws, uint32_t* hits, uint64_t* partials, int blocks,
+                                   const PartWs& ws, uint32_t* hits, uint64_t* partials, int blocks,
                                    hipStream_t s, PassRecorder* rec = nullptr);
 // Partitioned COBS probe (xs_probe_cobspart.hip) for classic banks of <= 128
 // docs (16-B rows) larger than the Infinity Cache.
 constexpr uint64_t kCobsPartMinKmers = 1ull << 23;  // default mode: smaller batches take the direct probe
 constexpr uint64_t kCobsPartMinBankMiB = 32;         // default mode: smaller banks take the direct probe
-struct CobsPartPlan {
-    uint32_t ck;         // k-mers per bucket block (1024, 2048 or 4096)
+struct CobsPartPlan : PartSizes {
     uint32_t shift;      // log2 rows per partition
     uint32_t P;          // partitions
-    uint64_t nblk;       // bucket blocks (>= the call's k-mers / ck)
+    uint64_t nblk;       // bucket blocks (>= the call's k-mers / kCobsCK)
     uint64_t rblk;       // bucket blocks per range (one workspace, reused range after range)
-    uint64_t kbound;     // upper bound of the call's sampled k-mers
     uint32_t pad;        // each partition's run of a block padded to a multiple of pad entries (1 or 4)
-    uint64_t stride;     // entries per bucket block region (ck * h, plus the padding, multiple of 8)
-    size_t entry_bytes, tbl_bytes, nkc_bytes, scan_bytes, aux_bytes;
+    uint64_t stride;     // entries per bucket block region (kCobsCK * h, plus the padding, multiple of 8)
 };
 // Runs are padded (64-B aligned rows) only while P <= kCobsPadParts: the pad
 // slots live in the bucket block's LDS.
 constexpr uint32_t kCobsPadParts = 512;
 constexpr uint32_t kCobsPadEntry = 0xFFFFFFFFu;  // pad slot: the lookup writes an all-ones row
-struct PartWs {
-    uint64_t* nkc;       // n+1 per-read k-mer counts
-    uint64_t* kofs;      // n+1 exclusive scan: first k-mer id of each read
-    void* scan_tmp;
-    size_t scan_bytes;
-    void* entries;       // a range's u32 entries (row in partition << id bits | k-mer in block), then their 16-B rows
-    uint16_t* tbl;       // (P+1) x rblk partition starts per bucket block, + block-major copy
-    uint32_t* aux;       // bucket block -> read holding its first k-mer, then per-partition queue counters
-};
 // False when the direct probe should run (bank not classic 16-B rows, under
 // kCobsPartMinBankMiB, h > 8, fewer than kCobsPartMinKmers k-mers in the call, or
 // opt.cobs_part = 0).
 bool cobs_part_plan(const CobsView& bv, uint32_t k, uint64_t n, uint64_t seq_bytes, uint32_t step,
-                    const ProbeOptions& opt, CobsPartPlan* plan);
+                    const ProbeOptions& opt, CobsPartPlan* plan = nullptr);  // null: the answer alone
 hipError_t launch_probe_cobs_part(const ReadView& rv, const CobsView& bv, const CobsPartPlan& plan,
                                   const PartWs& ws, uint32_t* hits, uint64_t* partials, int blocks,
                                   hipStream_t s, PassRecorder* rec = nullptr);

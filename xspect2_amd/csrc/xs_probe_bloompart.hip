@@ -25,11 +25,9 @@
 // A k-mer is a member iff none of its K bits is zero: the same answer as
 // rbloom's `kmer in bf` (probabilistic_single_filter_model.py:122-124), which
 // stops at the first zero bit.  Parity: tests/test_gpu_parity.py (rbloom
-// cases run through this path and the direct one).
-#include <hipcub/hipcub.hpp>
-
-#include <algorithm>
-
+// cases run through this path and the direct one).  The pieces shared with the
+// COBS probe (a bucket block's reads, the lookup's groups, the plan's common
+// sizes) are in xs_part.h.
 #include "xs_part.h"
 
 namespace xs {
@@ -39,7 +37,7 @@ namespace {
 template <int KT, int KB>
 __global__ void __launch_bounds__(kBucketThreads) bloom_bucket_kernel(ReadView rv, BloomView bv,
                                                                       const uint64_t* __restrict__ kofs,
-                                                                      uint32_t shift, uint32_t P, uint64_t tstride,
+                                                                      uint32_t shift, uint32_t P,
                                                                       uint32_t* __restrict__ eoff,
                                                                       uint16_t* __restrict__ eid,
                                                                       uint16_t* __restrict__ tbm,
@@ -61,59 +59,21 @@ __global__ void __launch_bounds__(kBucketThreads) bloom_bucket_kernel(ReadView r
     if (g0 >= Nk) return;  // uniform per block
     const uint32_t m = (uint32_t)min((uint64_t)kTK, Nk - g0);
     for (uint32_t i = tid; i < kPartMax; i += kBucketThreads) cur[i] = 0;
-    // reads of this block: from the one holding k-mer g0 to the one holding the
-    // next block's first k-mer (or the last read); their k-mer and byte
-    // offsets go to LDS when they fit, so a k-mer costs one global load (its
-    // window) and every thread's windows are in flight together
+    // the block's reads, staged in LDS when they fit, and the k-mer -> read map (s_off is
+    // free until the entries are placed)
     const uint64_t lo = blk_read[blockIdx.x];
     const uint64_t hi = g0 + kTK < Nk ? blk_read[blockIdx.x + 1] : rv.n - 1;
-    const uint64_t nr = hi - lo + 2;  // kofs/offs entries lo .. hi+1
-    const bool staged = nr <= kStageReads;
-    // k-mer -> read (staged case) by a block-wide max-scan of the reads' first k-mers, as in
-    // the COBS bucket pass (xs_probe_cobspart.hip); s_off is free until the entries are placed
     uint32_t* s_map = s_off;
-    if (staged) {
-        for (uint32_t x = tid; x < nr; x += kBucketThreads) {
-            s_kofs[x] = kofs[lo + x];
-            s_offs[x] = rv.offs[lo + x];
-        }
-        for (uint32_t i = tid; i < kTK; i += kBucketThreads) s_map[i] = 0;  // read 0 holds k-mer g0
-    }
-    __syncthreads();
-    if (staged) {
-        for (uint32_t x = 1 + tid; x + 1 < nr; x += kBucketThreads) {
-            const uint64_t st = s_kofs[x] - g0;
-            if (st < (uint64_t)kTK) atomicMax(&s_map[st], x);
-        }
-        __syncthreads();
-        uint32_t mv[PER];
-#pragma unroll
-        for (int q = 0; q < PER; ++q) mv[q] = s_map[tid * PER + q];
-        Scan(scan_tmp).InclusiveScan(mv, mv, hipcub::Max());
-#pragma unroll
-        for (int q = 0; q < PER; ++q) s_map[tid * PER + q] = mv[q];
-        __syncthreads();
-    }
+    const bool staged =
+        part_stage_reads<kTK, kBucketThreads, Scan>(rv, kofs, g0, lo, hi, s_kofs, s_offs, s_map, scan_tmp);
     const uint64_t omask = (1ull << shift) - 1;
     Kmer c[PER];
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const uint32_t i = tid + q * kBucketThreads;
         if (i < m) {
-            const uint64_t g = g0 + i;
-            uint64_t r, o0, o1, kr;
-            if (staged) {
-                const uint32_t a = s_map[i];  // largest x with s_kofs[x] <= g
-                kr = s_kofs[a];
-                o0 = s_offs[a];
-                o1 = s_offs[a + 1];
-            } else {
-                r = read_of(kofs, lo, hi, g);
-                kr = kofs[r];
-                o0 = rv.offs[r];
-                o1 = rv.offs[r + 1];
-            }
-            kmer_at<KT, kKmerBio>(rv, o0, o1 - o0, (g - kr) * rv.step, k, c[q]);
+            const KmerWindow w = part_kmer_window(rv, kofs, staged, s_map, s_kofs, s_offs, lo, hi, g0, i);
+            kmer_at<KT, kKmerBio>(rv, w.o0, w.len, w.pos, k, c[q]);
         }
     }
     uint64_t idx[PER][NK];  // the K bit indices of this thread's k-mers stay in registers,
@@ -188,8 +148,8 @@ __global__ void __launch_bounds__(kBucketThreads) bloom_bucket_kernel(ReadView r
 // sits on its own 128-B line (a line's atomics are serialised at the memory
 // side).  Every lane keeps kLookupUnroll entries in flight.
 
-// Each group's entry -> block map is built in LDS per window of W entries, as
-// in cobs_lookup_kernel (xs_probe_cobspart.hip): every lane writes its block's
+// Each group's entry -> block map is built in LDS per window of W entries
+// (xs_part.h, shared with cobs_lookup_kernel): every lane writes its block's
 // position base over its run's slots, then each entry reads its base back
 // (positions are u32: the host keeps a call under 2^32 entries).
 template <int kLookupUnroll, int W>
@@ -210,54 +170,33 @@ __global__ void __launch_bounds__(256) bloom_lookup_kernel(BloomView bv, const u
         const uint16_t* t0 = tbl + p * tstride;
         const uint16_t* t1 = t0 + tstride;
         for (;;) {
-            uint32_t grp = 0;
-            if (lane == 0) grp = atomicAdd(&qctr[p * kQStride], 1u);
-            const uint64_t b0 = (uint64_t)__builtin_amdgcn_readfirstlane(grp) * 64;
+            const uint64_t b0 = part_take_group(qctr, p, lane) * 64;
             if (b0 >= nblk) break;
-        {
             const uint64_t b = b0 + lane;
-            uint32_t s = 0, len = 0;
-            if (b < nblk) {
-                s = t0[b];
-                len = (uint32_t)t1[b] - s;
-            }
-            uint32_t inc = len;
+            const GroupRun g = part_group_run(t0, t1, b, b < nblk, cap, lane);
+            for (uint32_t w0 = 0; w0 < g.total; w0 += W) {
+                const uint32_t wend = min(g.total, w0 + W);
+                part_window_bases(s_base[wid], g, w0, wend);
+                for (uint32_t i0 = w0; i0 < wend; i0 += 64 * kLookupUnroll) {
+                    uint64_t pos[kLookupUnroll];
+                    uint32_t off[kLookupUnroll], w[kLookupUnroll];
 #pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t t = (uint32_t)__shfl_up((int)inc, d, 64);
-                if (lane >= d) inc += t;
-            }
-            const uint32_t pre = inc - len;
-            const uint32_t total = (uint32_t)__shfl((int)inc, 63, 64);
-            const uint32_t base = (uint32_t)(b * cap + s) - pre;  // entry i sits at base + i (mod 2^32)
-            for (uint32_t w0 = 0; w0 < total; w0 += W) {
-            const uint32_t wend = min(total, w0 + W);
-            {
-                const uint32_t lo = max(pre, w0), hi = min(pre + len, wend);
-                for (uint32_t x = lo; x < hi; ++x) s_base[wid][x - w0] = base;
-                __builtin_amdgcn_wave_barrier();
-            }
-            for (uint32_t i0 = w0; i0 < wend; i0 += 64 * kLookupUnroll) {
-                uint64_t pos[kLookupUnroll];
-                uint32_t off[kLookupUnroll], w[kLookupUnroll];
+                    for (int u = 0; u < kLookupUnroll; ++u) {
+                        const uint32_t i = i0 + u * 64 + lane;
+                        pos[u] = i < wend ? s_base[wid][i - w0] + i : 0u;
+                    }
 #pragma unroll
-                for (int u = 0; u < kLookupUnroll; ++u) {
-                    const uint32_t i = i0 + u * 64 + lane;
-                    pos[u] = i < wend ? s_base[wid][i - w0] + i : 0u;
+                    for (int u = 0; u < kLookupUnroll; ++u)
+                        off[u] = i0 + u * 64 + lane < wend ? eoff[pos[u]] : 0u;
+#pragma unroll
+                    for (int u = 0; u < kLookupUnroll; ++u)
+                        w[u] = i0 + u * 64 + lane < wend ? pb[off[u] >> 5] : ~0u;
+#pragma unroll
+                    for (int u = 0; u < kLookupUnroll; ++u)
+                        if (!((w[u] >> (off[u] & 31)) & 1u)) emiss[pos[u]] = 1;
                 }
-#pragma unroll
-                for (int u = 0; u < kLookupUnroll; ++u)
-                    off[u] = i0 + u * 64 + lane < wend ? eoff[pos[u]] : 0u;
-#pragma unroll
-                for (int u = 0; u < kLookupUnroll; ++u)
-                    w[u] = i0 + u * 64 + lane < wend ? pb[off[u] >> 5] : ~0u;
-#pragma unroll
-                for (int u = 0; u < kLookupUnroll; ++u)
-                    if (!((w[u] >> (off[u] & 31)) & 1u)) emiss[pos[u]] = 1;
+                __builtin_amdgcn_wave_barrier();  // bases read before the next window's writes
             }
-            __builtin_amdgcn_wave_barrier();  // bases read before the next window's writes
-            }
-        }
         }
     }
 }
@@ -348,18 +287,6 @@ __global__ void __launch_bounds__(256) bloom_count_kernel(ReadView rv, const uin
 
 }  // namespace
 
-// Partition shift for a filter of `mbits` bits: 2^24-bit (2 MiB) partitions
-// (2 MiB: 8.92 ms per config-2 step; 1 MiB 9.31, 512 KiB 10.86, 4 MiB 10.00),
-// halved down to 2^20 bits while that leaves fewer than 64 partitions (8 per
-// XCD keep the XCDs evenly loaded), doubled while more than kPartMax.
-static uint32_t part_shift(uint64_t mbits, uint32_t pref, uint32_t floor) {
-    auto parts = [mbits](uint32_t s) { return (mbits + (1ull << s) - 1) >> s; };
-    uint32_t s = pref;
-    while (s > floor && parts(s) < 64) --s;
-    while (parts(s) > kPartMax) ++s;
-    return s;
-}
-
 // opt.bloom_part (ProbeOptions): 0 = direct probe only; 1 (default) =
 // partitioned probe for filters of >= 16 MiB on member-rich input; 2 =
 // partitioned for such filters whatever the input; 3 = partitioned for every
@@ -371,28 +298,28 @@ bool bloom_part_plan(const BloomView& bv, uint64_t n, uint64_t seq_bytes, uint32
     if (mode <= 0 || bv.K == 0 || bv.K > (uint32_t)kPartKMax) return false;
     // member-poor input: the direct probe's early exit (2 bits first) wins
     if (mode == 1 && member_frac < kPartMinMembers) return false;
+    // 2^24-bit (2 MiB) partitions (2 MiB: 8.92 ms per config-2 step; 1 MiB 9.31, 512 KiB
+    // 10.86, 4 MiB 10.00), down to 2^20 bits while that leaves fewer than 64
     const uint32_t shift = mode >= 3 ? part_shift(bv.mbits, 10, 10) : part_shift(bv.mbits, 24, 20);
     const uint64_t P = (bv.mbits + (1ull << shift) - 1) >> shift;
     // filters under 16 MiB stay L2/MALL resident: the direct probe is faster there
     if ((mode < 3 && bv.mbits < (128ull << 20)) || shift > 32) return false;
-    const uint64_t kbound = seq_bytes / step + n + 1;  // >= sum of ceil((len-k+1)/step)
+    const uint64_t kbound = part_kbound(n, seq_bytes, step);
     if (kbound >= (1ull << 32)) return false;
     const uint64_t nblk = (kbound + kTK - 1) / kTK;
+    const uint64_t entry_bytes = nblk * kTK * bv.K * (sizeof(uint32_t) + sizeof(uint16_t) + sizeof(uint8_t));
+    // entries are transient: cap the workspace (larger batches take the direct probe);
+    // the lookup's u32 entry positions need fewer than 2^32 entries (7 B each: the cap keeps them)
+    if (entry_bytes > (24ull << 30) || nblk * kTK * bv.K >= (1ull << 32)) return false;
+    if (!plan) return true;
     plan->shift = shift;
     plan->P = (uint32_t)P;
     plan->tstride = nblk;
-    plan->kbound = kbound;
-    plan->entry_bytes = nblk * kTK * bv.K * (sizeof(uint32_t) + sizeof(uint16_t) + sizeof(uint8_t));
+    plan->entry_bytes = entry_bytes;
     plan->tbl_bytes = 2 * (P + 1) * nblk * sizeof(uint16_t);  // partition-major + block-major
     plan->miss_bytes = nblk * (kTK / 32) * sizeof(uint32_t);
-    plan->aux_bytes = (nblk + 1 + kQStride) * sizeof(uint32_t) + (size_t)P * kQStride * sizeof(uint32_t);
-    plan->nkc_bytes = (n + 1) * sizeof(uint64_t);
-    size_t sb = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n + 1));
-    plan->scan_bytes = sb;
-    // entries are transient: cap the workspace (larger batches take the direct probe);
-    // the lookup's u32 entry positions need fewer than 2^32 entries (7 B each: the cap keeps them)
-    return plan->entry_bytes <= (24ull << 30) && nblk * kTK * bv.K < (1ull << 32);
+    part_plan_sizes(plan, n, kbound, nblk, P);
+    return true;
 }
 
 // Entries in flight per lane: 4 / 8 / 16 measured 10.67 / 10.59 / 10.44 ms per
@@ -407,28 +334,11 @@ constexpr int kLookupPerCu = 3;
 // per lane 5.09 / 5.21; profiles/r03_lookup_ownermap.txt)
 constexpr int kLookupWindow = 1024;
 
-static int lookup_grid() {
-    static std::atomic<int> cache{0};
-    return cached_grid(cache, [] {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        int per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 768;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bloom_lookup_kernel<kUnroll, kLookupWindow>, 256, 0) !=
-                hipSuccess || per_cu < 1)
-            per_cu = 1;
-        const int g = std::min(per_cu, kLookupPerCu) * prop.multiProcessorCount;
-        return g >= 8 ? g / 8 * 8 : 8;  // whole groups of 8 blocks (one per XCD)
-    });
-}
-
 hipError_t launch_probe_bloom_part(const ReadView& rv, const BloomView& bv, const BloomPartPlan& plan,
-                                   const BloomPartWs& ws, uint32_t* hits, uint64_t* partials, int blocks,
+                                   const PartWs& ws, uint32_t* hits, uint64_t* partials, int blocks,
                                    hipStream_t s, PassRecorder* rec) {
     pass_mark(rec, kPassStart, s);
-    part_counts_kernel<<<grid_for(rv.n + 1, 256, 4096), 256, 0, s>>>(rv.offs, rv.n, rv.k, rv.step, ws.nkc);
-    size_t sb = ws.scan_bytes;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(ws.scan_tmp, sb, ws.nkc, ws.kofs, (int)(rv.n + 1), s);
+    hipError_t e = part_launch_counts(rv, ws, s);
     if (e != hipSuccess) return e;
     const uint64_t ne = plan.tstride * kTK * bv.K;
     uint32_t* eoff = reinterpret_cast<uint32_t*>(ws.entries);
@@ -439,18 +349,17 @@ hipError_t launch_probe_bloom_part(const ReadView& rv, const BloomView& bv, cons
     uint16_t* tbm = ws.tbl + (uint64_t)(plan.P + 1) * plan.tstride;  // block-major copy
     part_map_kernel<<<grid_for(rv.n, 256, 4096), 256, 0, s>>>(ws.kofs, rv.n, blk_read);
     pass_mark(rec, kPassPrep, s);
-    if (rv.k == 21 && bv.K == 7)
-        bloom_bucket_kernel<21, 7><<<(unsigned)plan.tstride, kBucketThreads, 0, s>>>(
-            rv, bv, ws.kofs, plan.shift, plan.P, plan.tstride, eoff, eid, tbm, blk_read);
-    else
-        bloom_bucket_kernel<0, 0><<<(unsigned)plan.tstride, kBucketThreads, 0, s>>>(
-            rv, bv, ws.kofs, plan.shift, plan.P, plan.tstride, eoff, eid, tbm, blk_read);
+    auto bucket = rv.k == 21 && bv.K == 7 ? bloom_bucket_kernel<21, 7> : bloom_bucket_kernel<0, 0>;
+    bucket<<<(unsigned)plan.tstride, kBucketThreads, 0, s>>>(rv, bv, ws.kofs, plan.shift, plan.P, eoff, eid, tbm,
+                                                             blk_read);
     part_transpose_kernel<<<dim3((unsigned)((plan.tstride + 63) / 64), (plan.P + 1 + 63) / 64), 256, 0, s>>>(
         tbm, plan.P + 1, plan.tstride, ws.tbl, 0, plan.tstride);
-    uint32_t* qctr = ws.aux + (plan.tstride + 1 + kQStride - 1) / kQStride * kQStride;  // 128-B aligned
+    uint32_t* qctr = part_queue_counters(ws, plan.tstride);
     if ((e = hipMemsetAsync(qctr, 0, (size_t)plan.P * kQStride * sizeof(uint32_t), s)) != hipSuccess) return e;
     pass_mark(rec, kPassBucket, s);
-    bloom_lookup_kernel<kUnroll, kLookupWindow><<<lookup_grid(), 256, 0, s>>>(
+    static std::atomic<int> grid_cache{0};
+    const int grid = part_lookup_grid(grid_cache, bloom_lookup_kernel<kUnroll, kLookupWindow>, kLookupPerCu);
+    bloom_lookup_kernel<kUnroll, kLookupWindow><<<grid, 256, 0, s>>>(
         bv, ws.kofs, rv.n, bv.K, plan.shift, plan.P, plan.tstride, eoff, ws.tbl, emiss, qctr);
     pass_mark(rec, kPassLookup, s);
     bloom_resolve_kernel<<<(unsigned)plan.tstride, 256, 0, s>>>(ws.kofs, rv.n, bv.K, eid, emiss, ws.miss);

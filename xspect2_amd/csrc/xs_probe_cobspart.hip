@@ -8,7 +8,7 @@
 // probe is (xs_probe_bloompart.hip):
 //
 //   counts  : per read k-mer count, exclusive scan -> global k-mer id g
-//   bucket  : one block per CK (default 2048) k-mers: canonical k-mer, the h
+//   bucket  : one block per kCobsCK (2048) k-mers: canonical k-mer, the h
 //             XXH64 rows (exactly as the direct probe), each binned by bank
 //             partition (2 MiB of rows) with one LDS atomic (its rank), a
 //             block scan and LDS-sorted placement; one u32 entry per row =
@@ -29,19 +29,36 @@
 // Same answer as the direct probe and the oracle (score[d] = number of
 // sampled positions whose h rows all hold bit d; probabilistic_filter_model.py
 // :227 -> cobs Search.search).  Parity: tests/test_gpu_parity.py runs the
-// classic cases through both paths.
+// classic cases through both paths.  The pieces shared with the rbloom probe
+// (a bucket block's reads, the lookup's groups, the plan's common sizes) are in
+// xs_part.h.
 #include "xs_part.h"
 
 namespace xs {
 
 namespace {
 
-// CK k-mers per bucket block (kCobsCK = 2048); an entry's low IDB bits name
-// its k-mer within the block.
+// Bucket blocks of 2048 k-mers: 12.71-12.85 ms per config-2 step against 13.81
+// at 1024 and 14.4 at 4096 when measured.  The
+// constants below go with that size.
+constexpr uint32_t kCobsCK = 2048;
+// The three rules below stay functions of the block size, in this form: the
+// tests' layout helper (tests/partition_layouts.py) reads them from this file.
+// Only kCobsCK is instantiated; the kernels use the named constants.
 template <int CK>
 constexpr int id_bits() { return CK == 4096 ? 12 : CK == 2048 ? 11 : 10; }
 template <int CK>
-constexpr int bucket_threads() { return CK / 2 < 1024 ? CK / 2 : 1024; }
+constexpr uint32_t cnt_reads() { return CK / 64; }
+template <int CK>
+constexpr uint32_t emb_max_docs() { return 128 - id_bits<CK>(); }
+constexpr int kCobsIdBits = id_bits<kCobsCK>();  // an entry's low bits name its k-mer within the block
+static_assert(1u << kCobsIdBits == kCobsCK, "an entry's id bits hold exactly a block's k-mers");
+constexpr int kCobsBucketThreads = 1024;
+constexpr int kCobsResolveThreads = 512;
+constexpr uint32_t kCobsCntReads = cnt_reads<kCobsCK>();  // reads per block with LDS counters (resolve pass)
+// With D <= kCobsEmbMaxDocs the entry's k-mer id rides in the row's unused top
+// bits (docs 118..127), so the resolve pass need not read the entries again.
+constexpr uint32_t kCobsEmbMaxDocs = emb_max_docs<kCobsCK>();
 constexpr int kMaxH = 8;     // rows per k-mer on this path
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -56,19 +73,19 @@ struct PartBank {
     uint32_t D, nwords;
 };
 
-template <int KT, int HT, int CK>
-__global__ void __launch_bounds__(bucket_threads<CK>(), CK == 4096 ? 1 : 2) cobs_bucket_kernel(ReadView rv, PartBank pb, uint32_t h,
-                                                                     const uint64_t* __restrict__ kofs,
-                                                                     uint32_t shift, uint32_t P,
-                                                                     uint32_t* __restrict__ ent,
-                                                                     uint16_t* __restrict__ tbm,
-                                                                     const uint32_t* __restrict__ blk_read,
-                                                                     uint64_t b_begin, uint64_t stride, uint32_t pad) {
+template <int KT, int HT>
+__global__ void __launch_bounds__(kCobsBucketThreads, 2) cobs_bucket_kernel(ReadView rv, PartBank pb, uint32_t h,
+                                                                            const uint64_t* __restrict__ kofs,
+                                                                            uint32_t shift, uint32_t P,
+                                                                            uint32_t* __restrict__ ent,
+                                                                            uint16_t* __restrict__ tbm,
+                                                                            const uint32_t* __restrict__ blk_read,
+                                                                            uint64_t b_begin, uint64_t stride,
+                                                                            uint32_t pad) {
     // entries and partition starts of block B go to row B - b_begin of the range's workspace;
     // with pad = 4 each partition's run is padded with kCobsPadEntry slots to a multiple
     // of 4 entries, so that the lookup's row runs are whole 64-B pieces (P <= kCobsPadParts)
-    constexpr int BT = bucket_threads<CK>();
-    constexpr int IDB = id_bits<CK>();
+    constexpr int CK = kCobsCK, BT = kCobsBucketThreads, IDB = kCobsIdBits;
     using Scan = hipcub::BlockScan<uint32_t, BT>;
     constexpr int ITEMS = kPartMax / BT;
     constexpr int PER = CK / BT;  // k-mers per thread
@@ -86,58 +103,19 @@ __global__ void __launch_bounds__(bucket_threads<CK>(), CK == 4096 ? 1 : 2) cobs
     if (g0 >= Nk) return;  // uniform per block
     const uint32_t m = (uint32_t)min((uint64_t)CK, Nk - g0);
     for (uint32_t i = tid; i < kPartMax; i += BT) cur[i] = 0;
-    // reads of this block staged in LDS when they fit (one global load per k-mer: its window)
+    // the block's reads, staged in LDS when they fit, and the k-mer -> read map (s_ent is
+    // free until the entries are placed)
     const uint64_t lo = blk_read[B];
     const uint64_t hi = g0 + CK < Nk ? blk_read[B + 1] : rv.n - 1;
-    const uint64_t nr = hi - lo + 2;
-    const bool staged = nr <= kStageReads;
-    // k-mer -> read (staged case): s_map[i] = the block-local read of k-mer g0 + i, from
-    // each read's first k-mer marked and a block-wide max-scan (s_ent is free until the
-    // entries are placed)
     uint32_t* s_map = s_ent;
-    if (staged) {
-        for (uint32_t x = tid; x < nr; x += BT) {
-            s_kofs[x] = kofs[lo + x];
-            s_offs[x] = rv.offs[lo + x];
-        }
-        for (uint32_t i = tid; i < CK; i += BT) s_map[i] = 0;  // read 0 holds k-mer g0
-    }
-    __syncthreads();
-    if (staged) {
-        // reads 1 .. nr-2 start inside the block or after it; empty reads share a start
-        // with the next read, and the max keeps the later one
-        for (uint32_t x = 1 + tid; x + 1 < nr; x += BT) {
-            const uint64_t st = s_kofs[x] - g0;
-            if (st < (uint64_t)CK) atomicMax(&s_map[st], x);
-        }
-        __syncthreads();
-        uint32_t mv[PER];
-#pragma unroll
-        for (int q = 0; q < PER; ++q) mv[q] = s_map[tid * PER + q];
-        Scan(scan_tmp).InclusiveScan(mv, mv, hipcub::Max());
-#pragma unroll
-        for (int q = 0; q < PER; ++q) s_map[tid * PER + q] = mv[q];
-        __syncthreads();
-    }
+    const bool staged = part_stage_reads<CK, BT, Scan>(rv, kofs, g0, lo, hi, s_kofs, s_offs, s_map, scan_tmp);
     Kmer c[PER];
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const uint32_t i = tid + q * BT;
         if (i < m) {
-            const uint64_t g = g0 + i;
-            uint64_t kr, o0, o1;
-            if (staged) {
-                const uint32_t a = s_map[i];  // largest x with s_kofs[x] <= g
-                kr = s_kofs[a];
-                o0 = s_offs[a];
-                o1 = s_offs[a + 1];
-            } else {
-                const uint64_t r = read_of(kofs, lo, hi, g);
-                kr = kofs[r];
-                o0 = rv.offs[r];
-                o1 = rv.offs[r + 1];
-            }
-            kmer_at<KT, kKmerCobs>(rv, o0, o1 - o0, (g - kr) * rv.step, k, c[q]);
+            const KmerWindow w = part_kmer_window(rv, kofs, staged, s_map, s_kofs, s_offs, lo, hi, g0, i);
+            kmer_at<KT, kKmerCobs>(rv, w.o0, w.len, w.pos, k, c[q]);
         }
     }
     uint32_t row[PER][NH];  // the h rows of this thread's k-mers stay in registers,
@@ -208,11 +186,9 @@ __global__ void __launch_bounds__(bucket_threads<CK>(), CK == 4096 ? 1 : 2) cobs
 // the XCD's L2 while the entries stream past), taking groups of gb <= 64
 // bucket blocks from the partition's queue counter (the rbloom lookup's
 // scheme, xs_probe_bloompart.hip; gb shrinks for short ranges so that a
-// partition still has a group for every wave of its XCD).  Each entry's row goes back in entry order; with
-// EMB (D <= kEmbMaxDocs) the entry's k-mer id rides in the row's unused top
-// bits (docs 118..127), so the resolve pass need not read the entries again.
-template <int CK>
-constexpr uint32_t emb_max_docs() { return 128 - id_bits<CK>(); }
+// partition still has a group for every wave of its XCD; the group code is
+// xs_part.h's).  Each entry's row goes back in entry order; with EMB (D <=
+// kCobsEmbMaxDocs) the entry's k-mer id rides in the row's top bits.
 // Rows are gathered by LDS-DMA (global_load_lds_dwordx4) into per-wave slots,
 // one gather instruction in flight per wave: 1 in flight x 2 workgroups per CU
 // beat 2, 3 or 6 in flight and 1, 3 or 4 workgroups (more requests per CU only
@@ -232,7 +208,7 @@ constexpr int kLookupUnroll = 8;
 constexpr int kLookupWin = 2048;
 constexpr int kLookupPerCu = 2;
 
-template <bool EMB, int CK>
+template <bool EMB>
 __global__ void __launch_bounds__(256) cobs_lookup_kernel(PartBank pb, const uint64_t* __restrict__ kofs,
                                                           uint64_t n, uint32_t H, uint32_t shift, uint32_t P,
                                                           uint64_t tstride, const uint32_t* __restrict__ ent,
@@ -240,7 +216,7 @@ __global__ void __launch_bounds__(256) cobs_lookup_kernel(PartBank pb, const uin
                                                           uint4* __restrict__ out, uint32_t* qctr,
                                                           uint64_t b_begin, uint64_t b_end, uint32_t gb,
                                                           uint64_t stride) {
-    constexpr int IDB = id_bits<CK>();
+    constexpr int CK = kCobsCK, IDB = kCobsIdBits;
     constexpr int U = kLookupUnroll;
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
@@ -256,33 +232,13 @@ __global__ void __launch_bounds__(256) cobs_lookup_kernel(PartBank pb, const uin
         const uint16_t* t0 = tbl + p * tstride;
         const uint16_t* t1 = t0 + tstride;
         for (;;) {
-            uint32_t grp = 0;
-            if (lane == 0) grp = atomicAdd(&qctr[p * kQStride], 1u);
-            const uint64_t b0 = (uint64_t)__builtin_amdgcn_readfirstlane(grp) * gb;
+            const uint64_t b0 = part_take_group(qctr, p, lane) * gb;
             if (b0 >= nblk) break;
             const uint64_t b = b0 + lane;
-            uint32_t s = 0, len = 0;
-            if ((uint32_t)lane < gb && b < nblk) {
-                s = t0[b];
-                len = (uint32_t)t1[b] - s;
-            }
-            uint32_t inc = len;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t t = (uint32_t)__shfl_up((int)inc, d, 64);
-                if (lane >= d) inc += t;
-            }
-            const uint32_t pre = inc - len;
-            const uint32_t total = (uint32_t)__shfl((int)inc, 63, 64);
-            // entry i of the group sits at its block's base + i (mod 2^32)
-            const uint32_t base = (uint32_t)(b * stride + s) - pre;
-            for (uint32_t w0 = 0; w0 < total; w0 += kLookupWin) {
-                const uint32_t wend = min(total, w0 + kLookupWin);
-                {
-                    const uint32_t lo = max(pre, w0), hi = min(pre + len, wend);
-                    for (uint32_t x = lo; x < hi; ++x) s_base[wid][x - w0] = base;
-                    __builtin_amdgcn_wave_barrier();
-                }
+            const GroupRun g = part_group_run(t0, t1, b, (uint32_t)lane < gb && b < nblk, stride, lane);
+            for (uint32_t w0 = 0; w0 < g.total; w0 += kLookupWin) {
+                const uint32_t wend = min(g.total, w0 + kLookupWin);
+                part_window_bases(s_base[wid], g, w0, wend);
                 for (uint32_t i0 = w0; i0 < wend; i0 += 64 * U) {
                     uint64_t pos[U];
                     uint32_t e[U];
@@ -338,26 +294,23 @@ __global__ void __launch_bounds__(256) cobs_lookup_kernel(PartBank pb, const uin
 // (at most two) reads crossing its edges are added atomically (hits zeroed
 // beforehand).  Blocks with more reads than LDS counter rows (short reads)
 // add every count atomically.
-template <int CK>
-constexpr int resolve_threads() { return CK / 4 < 1024 ? CK / 4 : 1024; }
-template <int CK>
-constexpr uint32_t cnt_reads() { return CK / 64; }  // reads per block with LDS counters
 constexpr int kResolveUnroll = 8;
 
-
-template <bool EMB, int CK>
-__global__ void __launch_bounds__(resolve_threads<CK>()) cobs_resolve_kernel(ReadView rv, const uint64_t* __restrict__ kofs,
-                                                                       uint32_t H, uint32_t D, uint32_t nwords,
-                                                                       const uint32_t* __restrict__ ent,
-                                                                       const uint4* __restrict__ rowv,
-                                                                       const uint32_t* __restrict__ blk_read,
-                                                                       uint32_t* __restrict__ hits,
-                                                                       uint64_t* __restrict__ partials, int pblocks,
-                                                                       uint64_t b_begin, uint64_t stride,
-                                                                       const uint16_t* __restrict__ tbm, uint32_t P1) {
+template <bool EMB>
+__global__ void __launch_bounds__(kCobsResolveThreads) cobs_resolve_kernel(ReadView rv,
+                                                                           const uint64_t* __restrict__ kofs,
+                                                                           uint32_t D, uint32_t nwords,
+                                                                           const uint32_t* __restrict__ ent,
+                                                                           const uint4* __restrict__ rowv,
+                                                                           const uint32_t* __restrict__ blk_read,
+                                                                           uint32_t* __restrict__ hits,
+                                                                           uint64_t* __restrict__ partials, int pblocks,
+                                                                           uint64_t b_begin, uint64_t stride,
+                                                                           const uint16_t* __restrict__ tbm,
+                                                                           uint32_t P1) {
+    constexpr int CK = kCobsCK, kResolveThreads = kCobsResolveThreads;
+    constexpr uint32_t kCntReads = kCobsCntReads;
     __shared__ uint32_t acc[4][CK];
-    constexpr int kResolveThreads = resolve_threads<CK>();
-    constexpr uint32_t kCntReads = cnt_reads<CK>();
     __shared__ uint32_t cnt[kCntReads][128];
     __shared__ uint64_t s_kofs[kCntReads + 1];
     __shared__ uint32_t s_tot[128];  // the block's per-doc totals (<= CK each)
@@ -386,8 +339,7 @@ __global__ void __launch_bounds__(resolve_threads<CK>()) cobs_resolve_kernel(Rea
     }
     __syncthreads();
     const uint64_t base = (B - b_begin) * stride;
-    const uint32_t tot = tbm[(B - b_begin) * P1 + P1 - 1];  // m * H, plus the pad slots (all-ones rows)
-    (void)H;
+    const uint32_t tot = tbm[(B - b_begin) * P1 + P1 - 1];  // m * h, plus the pad slots (all-ones rows)
     // kResolveUnroll rows in flight per lane, then their LDS ANDs
     for (uint32_t e0 = tid; e0 < tot; e0 += kResolveThreads * kResolveUnroll) {
         uint4 v[kResolveUnroll];
@@ -406,7 +358,7 @@ __global__ void __launch_bounds__(resolve_threads<CK>()) cobs_resolve_kernel(Rea
 #pragma unroll
         for (int u = 0; u < kResolveUnroll; ++u) {
             if (e0 + u * kResolveThreads < tot) {
-                const uint32_t i = EMB ? v[u].w >> (32 - id_bits<CK>()) : id[u];
+                const uint32_t i = EMB ? v[u].w >> (32 - kCobsIdBits) : id[u];
                 atomicAnd(&acc[0][i], v[u].x);
                 if (nwords > 1) atomicAnd(&acc[1][i], v[u].y);
                 if (nwords > 2) atomicAnd(&acc[2][i], v[u].z);
@@ -494,10 +446,10 @@ __global__ void __launch_bounds__(resolve_threads<CK>()) cobs_resolve_kernel(Rea
 // n x D matrix needs no memset: rows of reads without k-mers, of reads whose
 // k-mers span two bucket blocks (added atomically by each), and of every read
 // of a block with more reads than its LDS counter rows (all added atomically).
-template <int CK>
 __global__ void part_zero_rows_kernel(const uint64_t* __restrict__ kofs, uint64_t n,
                                       const uint32_t* __restrict__ blk_read, uint32_t D,
                                       uint32_t* __restrict__ hits) {
+    constexpr int CK = kCobsCK;
     const uint64_t Nk = kofs[n];
     for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < n;
          r += (uint64_t)gridDim.x * blockDim.x) {
@@ -507,7 +459,7 @@ __global__ void part_zero_rows_kernel(const uint64_t* __restrict__ kofs, uint64_
             const uint64_t b0 = a / CK, b1 = (e - 1) / CK;
             const uint64_t lo = blk_read[b0];
             const uint64_t hi = (b0 + 1) * CK < Nk ? blk_read[b0 + 1] : n - 1;
-            zero = b0 != b1 || hi - lo + 1 > cnt_reads<CK>();
+            zero = b0 != b1 || hi - lo + 1 > kCobsCntReads;
         }
         if (zero)
             for (uint32_t d = 0; d < D; ++d) hits[r * D + d] = 0;
@@ -515,10 +467,6 @@ __global__ void part_zero_rows_kernel(const uint64_t* __restrict__ kofs, uint64_
 }
 
 }  // namespace
-
-// Bucket blocks of 2048 k-mers: 12.71-12.85 ms per config-2 step against 13.81
-// at 1024 and 14.4 at 4096 when measured.
-constexpr uint32_t kCobsCK = 2048;
 
 // opt.cobs_part (ProbeOptions): 0 = direct probe only; 1 (default) = partitioned
 // probe for classic banks of <= 128 docs of at least kCobsPartMinBankMiB and
@@ -536,124 +484,45 @@ bool cobs_part_plan(const CobsView& bv, uint32_t k, uint64_t n, uint64_t seq_byt
     // banks that (nearly) fit the XCDs' L2s: the direct probe is as fast there
     // (15 MB: 11.09 vs 11.03 ms; 61 MB: 14.40 vs 11.53; profiles/r02_cobspart_banksize.txt)
     if (mode == 1 && sig * 16 < (kCobsPartMinBankMiB << 20)) return false;
-    const uint32_t ck = kCobsCK, idb = id_bits<kCobsCK>();
-    // 2^17 rows (2 MiB) per partition, fewer rows while that leaves under 64
-    // partitions (8 per XCD), more while over kPartMax
-    auto parts = [sig](uint32_t s) { return (sig + (1ull << s) - 1) >> s; };
-    uint32_t shift = mode == 4 ? 10 : 17;
-    const uint32_t floor_shift = mode >= 3 ? 10 : 13;
-    while (mode != 4 && shift > floor_shift && parts(shift) < 64) --shift;
-    while (parts(shift) > kPartMax) ++shift;
-    // entry = (row in partition << idb) | k-mer in block: at shift + idb == 32 the
+    // 2^17 rows (2 MiB) per partition, down to 2^13 (modes 3: 2^10) while that leaves
+    // under 64 partitions; mode 4: 2^10 rows whatever their number
+    const uint32_t shift = mode == 4 ? part_shift(sig, 10, 10) : part_shift(sig, 17, mode >= 3 ? 10 : 13);
+    // entry = (row in partition << id bits) | k-mer in block: at shift + id bits == 32 the
     // last row's last k-mer would encode to kCobsPadEntry (0xFFFFFFFF); sig < 2^30
     // and kPartMax partitions keep shift <= 20 (a guard, not a reachable case)
-    if (shift + idb >= 32) return false;
-    const uint64_t kbound = seq_bytes / step + n + 1;  // >= sum of ceil((len-k+1)/step)
+    if (shift + kCobsIdBits >= 32) return false;
+    const uint64_t kbound = part_kbound(n, seq_bytes, step);
     // small batches: the direct probe is faster below ~60-100 k reads of 150 bp
     // (profiles/r02_cobspart_small.txt)
     if (mode == 1 && kbound < kCobsPartMinKmers) return false;
-    const uint64_t nblk = (kbound + ck - 1) / ck;
-    const uint64_t P = parts(shift);
+    if (!plan) return true;
+    const uint64_t nblk = (kbound + kCobsCK - 1) / kCobsCK;
+    const uint64_t P = (sig + (1ull << shift) - 1) >> shift;
     // The bucket blocks run in ranges that reuse one workspace of at most
     // opt.workspace_mib MiB of entries + rows (default kCobsPartWsMiB), so
     // any batch size fits.  Runs are padded to 4 entries (64-B row pieces: 4.37
     // -> 3.51 ms for the lookup's write stream alone, tools/runwrite.hip) while
     // the pad slots fit the bucket block's LDS (P <= kCobsPadParts).
     const uint32_t pad = P <= kCobsPadParts ? 4 : 1;
-    const uint64_t stride = ((uint64_t)ck * bv.h + (pad - 1) * P + 7) / 8 * 8;
+    const uint64_t stride = ((uint64_t)kCobsCK * bv.h + (pad - 1) * P + 7) / 8 * 8;
     const uint64_t per_block = stride * (sizeof(uint32_t) + sizeof(uint4));
     const uint64_t cap = (uint64_t)std::max<uint32_t>(1, opt.workspace_mib) << 20;
     // a range holds fewer than 2^32 entries (the lookup's u32 positions)
     const uint64_t rblk = std::max<uint64_t>(1, std::min<uint64_t>({nblk, cap / per_block, ((1ull << 32) - 1) / stride}));
-    plan->ck = ck;
     plan->shift = shift;
     plan->P = (uint32_t)P;
     plan->nblk = nblk;
     plan->rblk = rblk;
-    plan->kbound = kbound;
     plan->pad = pad;
     plan->stride = stride;
     plan->entry_bytes = rblk * per_block + 128;                      // a range's entries, then their rows (128-B aligned)
     plan->tbl_bytes = 2 * (P + 1) * rblk * sizeof(uint16_t);         // partition- + block-major
-    plan->aux_bytes = (nblk + 1 + kQStride) * sizeof(uint32_t) + (size_t)P * kQStride * sizeof(uint32_t);
-    plan->nkc_bytes = (n + 1) * sizeof(uint64_t);
-    size_t sb = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n + 1));
-    plan->scan_bytes = sb;
+    part_plan_sizes(plan, n, kbound, nblk, P);
     return true;
-}
-
-static int cobs_lookup_grid() {
-    static std::atomic<int> cache{0};
-    return cached_grid(cache, [] {
-        int dev = 0, per_cu = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 768;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cobs_lookup_kernel<true, kCobsCK>, 256, 0) !=
-                hipSuccess || per_cu < 1)
-            per_cu = 1;
-        const int g = std::min(per_cu, kLookupPerCu) * prop.multiProcessorCount;
-        return g >= 8 ? g / 8 * 8 : 8;  // whole groups of 8 blocks (one per XCD)
-    });
 }
 
 // Ranges of plan.rblk bucket blocks, one after the other on stream s, each
 // through bucket -> transpose -> lookup -> resolve in the same workspace.
-template <int CK>
-static hipError_t cobs_part_pipeline(const ReadView& rv, const PartBank& pb, uint32_t H, const CobsPartPlan& plan,
-                                     const PartWs& ws, uint32_t* hits, uint64_t* partials, int blocks,
-                                     hipStream_t s, PassRecorder* rec) {
-    hipError_t e;
-    const uint64_t ne = plan.rblk * plan.stride;
-    uint32_t* ent = reinterpret_cast<uint32_t*>(ws.entries);
-    uint4* rowv = reinterpret_cast<uint4*>(ent + (ne + 31) / 32 * 32);
-    uint32_t* blk_read = ws.aux;
-    uint16_t* tbm = ws.tbl + (uint64_t)(plan.P + 1) * plan.rblk;  // block-major copy
-    uint32_t* qctr = ws.aux + (plan.nblk + 1 + kQStride - 1) / kQStride * kQStride;  // 128-B aligned
-    part_map_kernel<CK><<<grid_for(rv.n, 256, 4096), 256, 0, s>>>(ws.kofs, rv.n, blk_read);
-    if (hits)
-        part_zero_rows_kernel<CK><<<grid_for(rv.n, 256, 4096), 256, 0, s>>>(ws.kofs, rv.n, blk_read, pb.D, hits);
-    pass_mark(rec, kPassPrep, s);
-    const bool emb = pb.D <= emb_max_docs<CK>();
-    const int grid = cobs_lookup_grid();
-    // groups per partition >= the XCD's waves (grid / 8 workgroups x 4 waves)
-    const uint64_t waves = (uint64_t)grid / 8 * 4;
-    for (uint64_t b0 = 0; b0 < plan.nblk; b0 += plan.rblk) {
-        const uint64_t b1 = std::min(plan.nblk, b0 + plan.rblk);
-        const unsigned nb = (unsigned)(b1 - b0);
-        if (rv.k == 21 && H == 7)
-            cobs_bucket_kernel<21, 7, CK><<<nb, bucket_threads<CK>(), 0, s>>>(rv, pb, H, ws.kofs, plan.shift, plan.P,
-                                                                            ent, tbm, blk_read, b0, plan.stride,
-                                                                            plan.pad);
-        else
-            cobs_bucket_kernel<0, 0, CK><<<nb, bucket_threads<CK>(), 0, s>>>(rv, pb, H, ws.kofs, plan.shift, plan.P,
-                                                                           ent, tbm, blk_read, b0, plan.stride,
-                                                                           plan.pad);
-        part_transpose_kernel<<<dim3((nb + 63) / 64, (plan.P + 1 + 63) / 64), 256, 0, s>>>(
-            tbm, plan.P + 1, plan.rblk, ws.tbl, 0, nb);
-        if ((e = hipMemsetAsync(qctr, 0, (size_t)plan.P * kQStride * sizeof(uint32_t), s)) != hipSuccess) return e;
-        pass_mark(rec, kPassBucket, s);
-        const uint32_t gb = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (b1 - b0) / std::max<uint64_t>(1, waves)));
-        if (emb)
-            cobs_lookup_kernel<true, CK><<<grid, 256, 0, s>>>(pb, ws.kofs, rv.n, H, plan.shift, plan.P, plan.rblk, ent,
-                                                              ws.tbl, rowv, qctr, b0, b1, gb, plan.stride);
-        else
-            cobs_lookup_kernel<false, CK><<<grid, 256, 0, s>>>(pb, ws.kofs, rv.n, H, plan.shift, plan.P, plan.rblk,
-                                                               ent, ws.tbl, rowv, qctr, b0, b1, gb, plan.stride);
-        pass_mark(rec, kPassLookup, s);
-        if (emb)
-            cobs_resolve_kernel<true, CK><<<nb, resolve_threads<CK>(), 0, s>>>(
-                rv, ws.kofs, H, pb.D, pb.nwords, ent, rowv, blk_read, hits, partials, blocks, b0, plan.stride, tbm,
-                plan.P + 1);
-        else
-            cobs_resolve_kernel<false, CK><<<nb, resolve_threads<CK>(), 0, s>>>(
-                rv, ws.kofs, H, pb.D, pb.nwords, ent, rowv, blk_read, hits, partials, blocks, b0, plan.stride, tbm,
-                plan.P + 1);
-        pass_mark(rec, kPassResolve, s);
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_probe_cobs_part(const ReadView& rv, const CobsView& bv, const CobsPartPlan& plan,
                                   const PartWs& ws, uint32_t* hits, uint64_t* partials, int blocks,
                                   hipStream_t s, PassRecorder* rec) {
@@ -664,15 +533,47 @@ hipError_t launch_probe_cobs_part(const ReadView& rv, const CobsView& bv, const 
     pb.magic = barrett_magic(bv.sig0);
     pb.D = (uint32_t)bv.D;
     pb.nwords = (uint32_t)((bv.D + 31) / 32);
+    const uint32_t H = bv.h;
     hipError_t e;
     // (the hit rows the resolve does not store are zeroed by part_zero_rows_kernel)
     if (partials && (e = hipMemsetAsync(partials, 0, (size_t)blocks * (bv.D + 1) * sizeof(uint64_t), s)) != hipSuccess)
         return e;
-    part_counts_kernel<<<grid_for(rv.n + 1, 256, 4096), 256, 0, s>>>(rv.offs, rv.n, rv.k, rv.step, ws.nkc);
-    size_t sb = ws.scan_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(ws.scan_tmp, sb, ws.nkc, ws.kofs, (int)(rv.n + 1), s)) != hipSuccess)
-        return e;
-    return cobs_part_pipeline<kCobsCK>(rv, pb, bv.h, plan, ws, hits, partials, blocks, s, rec);
+    if ((e = part_launch_counts(rv, ws, s)) != hipSuccess) return e;
+    const uint64_t ne = plan.rblk * plan.stride;
+    uint32_t* ent = reinterpret_cast<uint32_t*>(ws.entries);
+    uint4* rowv = reinterpret_cast<uint4*>(ent + (ne + 31) / 32 * 32);
+    uint32_t* blk_read = ws.aux;
+    uint16_t* tbm = ws.tbl + (uint64_t)(plan.P + 1) * plan.rblk;  // block-major copy
+    uint32_t* qctr = part_queue_counters(ws, plan.nblk);
+    part_map_kernel<kCobsCK><<<grid_for(rv.n, 256, 4096), 256, 0, s>>>(ws.kofs, rv.n, blk_read);
+    if (hits) part_zero_rows_kernel<<<grid_for(rv.n, 256, 4096), 256, 0, s>>>(ws.kofs, rv.n, blk_read, pb.D, hits);
+    pass_mark(rec, kPassPrep, s);
+    const bool emb = pb.D <= kCobsEmbMaxDocs;
+    static std::atomic<int> grid_cache{0};
+    const int grid = part_lookup_grid(grid_cache, cobs_lookup_kernel<true>, kLookupPerCu);
+    // groups per partition >= the XCD's waves (grid / 8 workgroups x 4 waves)
+    const uint64_t waves = (uint64_t)grid / 8 * 4;
+    for (uint64_t b0 = 0; b0 < plan.nblk; b0 += plan.rblk) {
+        const uint64_t b1 = std::min(plan.nblk, b0 + plan.rblk);
+        const unsigned nb = (unsigned)(b1 - b0);
+        auto bucket = rv.k == 21 && H == 7 ? cobs_bucket_kernel<21, 7> : cobs_bucket_kernel<0, 0>;
+        bucket<<<nb, kCobsBucketThreads, 0, s>>>(rv, pb, H, ws.kofs, plan.shift, plan.P, ent, tbm, blk_read, b0,
+                                                 plan.stride, plan.pad);
+        part_transpose_kernel<<<dim3((nb + 63) / 64, (plan.P + 1 + 63) / 64), 256, 0, s>>>(
+            tbm, plan.P + 1, plan.rblk, ws.tbl, 0, nb);
+        if ((e = hipMemsetAsync(qctr, 0, (size_t)plan.P * kQStride * sizeof(uint32_t), s)) != hipSuccess) return e;
+        pass_mark(rec, kPassBucket, s);
+        const uint32_t gb = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (b1 - b0) / std::max<uint64_t>(1, waves)));
+        auto lookup = emb ? cobs_lookup_kernel<true> : cobs_lookup_kernel<false>;
+        lookup<<<grid, 256, 0, s>>>(pb, ws.kofs, rv.n, H, plan.shift, plan.P, plan.rblk, ent, ws.tbl, rowv, qctr, b0,
+                                    b1, gb, plan.stride);
+        pass_mark(rec, kPassLookup, s);
+        auto resolve = emb ? cobs_resolve_kernel<true> : cobs_resolve_kernel<false>;
+        resolve<<<nb, kCobsResolveThreads, 0, s>>>(rv, ws.kofs, pb.D, pb.nwords, ent, rowv, blk_read, hits, partials,
+                                                   blocks, b0, plan.stride, tbm, plan.P + 1);
+        pass_mark(rec, kPassResolve, s);
+    }
+    return hipGetLastError();
 }
 
 }  // namespace xs

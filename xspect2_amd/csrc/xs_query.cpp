@@ -57,10 +57,11 @@ void poll_member_frac(xs_bank* b) {
 }
 
 // The partitioned probes' workspace is transient: when HBM cannot hold it, the query takes
-// the direct / gather probe instead of failing (false).  miss = 0 (COBS): no miss bitmap.
-bool reserve_part_ws(xs_bank* b, size_t nkc, size_t scan, size_t entry, size_t tbl, size_t miss, size_t aux) {
-    if (b->pk_nkc.ensure(nkc) || b->pk_kofs.ensure(nkc) || b->pk_scan.ensure(scan) || b->pk_entries.ensure(entry) ||
-        b->pk_tbl.ensure(tbl) || (miss && b->pk_miss.ensure(miss)) || b->pk_aux.ensure(aux)) {
+// the direct / gather probe instead of failing (false).  miss_bytes = 0 (COBS): no miss bitmap.
+bool reserve_part_ws(xs_bank* b, const PartSizes& z) {
+    if (b->pk_nkc.ensure(z.nkc_bytes) || b->pk_kofs.ensure(z.nkc_bytes) || b->pk_scan.ensure(z.scan_bytes) ||
+        b->pk_entries.ensure(z.entry_bytes) || b->pk_tbl.ensure(z.tbl_bytes) ||
+        (z.miss_bytes && b->pk_miss.ensure(z.miss_bytes)) || b->pk_aux.ensure(z.aux_bytes)) {
         (void)hipGetLastError();
         return false;
     }
@@ -80,8 +81,7 @@ int xs::run_query(xs_bank* b, const Inputs& in, uint32_t step, uint32_t* d_hits,
     bool cobs_part = false;
     if (!bloom) {
         cobs_part = cobs_part_plan(b->cobs_view(), b->k, in.n, in.plan_bytes(), step, b->opt, &cplan) &&
-                    reserve_part_ws(b, cplan.nkc_bytes, cplan.scan_bytes, cplan.entry_bytes, cplan.tbl_bytes, 0,
-                                    cplan.aux_bytes);
+                    reserve_part_ws(b, cplan);
         (void)hipGetLastError();  // an earlier call's failure left on this thread is not this query's (the launchers read it)
     }
     ReadView rv;
@@ -108,31 +108,24 @@ int xs::run_query(xs_bank* b, const Inputs& in, uint32_t step, uint32_t* d_hits,
     BloomPartPlan plan;
     int path = XS_PATH_GATHER;
     const char* kernel = "";
-    if (bloom && bloom_part_plan(b->bloom_view(), in.n, in.plan_bytes(), step, b->member_frac, b->opt, &plan) &&
-        reserve_part_ws(b, plan.nkc_bytes, plan.scan_bytes, plan.entry_bytes, plan.tbl_bytes, plan.miss_bytes,
-                        plan.aux_bytes)) {
+    const bool bloom_part = bloom &&
+                            bloom_part_plan(b->bloom_view(), in.n, in.plan_bytes(), step, b->member_frac, b->opt, &plan) &&
+                            reserve_part_ws(b, plan);
+    if (bloom_part || cobs_part) {
         path = XS_PATH_PARTITIONED;
-        kernel = "bloompart";
-        const BloomPartWs ws{b->pk_nkc.as<uint64_t>(), b->pk_kofs.as<uint64_t>(), b->pk_scan.p, b->pk_scan.cap,
-                             b->pk_entries.as<uint64_t>(), b->pk_tbl.as<uint16_t>(), b->pk_miss.as<uint32_t>(),
-                             b->pk_aux.as<uint32_t>()};
+        kernel = bloom ? "bloompart" : "cobspart";
+        // pk_miss is the rbloom plans' alone: null on a COBS bank
+        const PartWs ws{b->pk_nkc.as<uint64_t>(), b->pk_kofs.as<uint64_t>(), b->pk_scan.p, b->pk_scan.cap,
+                        b->pk_entries.p, b->pk_tbl.as<uint16_t>(), b->pk_miss.as<uint32_t>(),
+                        b->pk_aux.as<uint32_t>()};
         PassRecorder rec{&b->pass_ev, &b->pass_tag, &b->pass_used};
-        HIPCHK(launch_probe_bloom_part(rv, b->bloom_view(), plan, ws, d_hits, partials, blocks, s,
-                                       b->profiling ? &rec : nullptr));
+        PassRecorder* prec = b->profiling ? &rec : nullptr;
+        HIPCHK(bloom ? launch_probe_bloom_part(rv, b->bloom_view(), plan, ws, d_hits, partials, blocks, s, prec)
+                     : launch_probe_cobs_part(rv, b->cobs_view(), cplan, ws, d_hits, partials, blocks, s, prec));
     } else if (bloom) {
         HIPCHK(launch_probe_bloom(rv, b->bloom_view(), d_hits, partials, blocks, s, &kernel));
     } else {
-        const CobsView cv = b->cobs_view();
-        if (cobs_part) {
-            path = XS_PATH_PARTITIONED;
-            kernel = "cobspart";
-            const PartWs ws{b->pk_nkc.as<uint64_t>(), b->pk_kofs.as<uint64_t>(), b->pk_scan.p, b->pk_scan.cap,
-                            b->pk_entries.p, b->pk_tbl.as<uint16_t>(), b->pk_aux.as<uint32_t>()};
-            PassRecorder rec{&b->pass_ev, &b->pass_tag, &b->pass_used};
-            HIPCHK(launch_probe_cobs_part(rv, cv, cplan, ws, d_hits, partials, blocks, s, b->profiling ? &rec : nullptr));
-        } else {
-            HIPCHK(launch_probe_cobs(rv, cv, d_hits, partials, blocks, s, &kernel));
-        }
+        HIPCHK(launch_probe_cobs(rv, b->cobs_view(), d_hits, partials, blocks, s, &kernel));
     }
     b->last_path = path;
     b->last_kernel = kernel;
@@ -468,14 +461,10 @@ int query_small(xs_bank* b, const char* seqs, const uint64_t* offsets, uint64_t 
     if (U > kSmallUnits) return XS_OK;
     // only where query_host would take the direct / gather probe as well (a forced
     // or member-rich partitioned path keeps its own pipeline)
-    if (bloom) {
-        poll_member_frac(b);
-        BloomPartPlan plan;
-        if (bloom_part_plan(b->bloom_view(), n, bytes, step, b->member_frac, b->opt, &plan)) return XS_OK;
-    } else {
-        CobsPartPlan plan;
-        if (cobs_part_plan(b->cobs_view(), b->k, n, bytes, step, b->opt, &plan)) return XS_OK;
-    }
+    if (bloom) poll_member_frac(b);
+    if (bloom ? bloom_part_plan(b->bloom_view(), n, bytes, step, b->member_frac, b->opt)
+              : cobs_part_plan(b->cobs_view(), b->k, n, bytes, step, b->opt))
+        return XS_OK;
     const int blocks = (int)std::min<uint64_t>((uint64_t)probe_grid(b), std::max<uint64_t>(1, (U + kSmallUnitsPerBlock - 1) / kSmallUnitsPerBlock));
     // device / pinned layout: [queue | offsets | unit_ofs | unit_read | seqs] [partials | hits]
     const size_t o_off = 16, o_uofs = o_off + align16((n + 1) * 8), o_uread = o_uofs + align16((n + 1) * 8);
