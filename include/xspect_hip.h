@@ -363,6 +363,66 @@ int xs_mlst_chunk_top_device(const uint32_t* d_hits, uint64_t n_chunks, uint64_t
                              const uint64_t* d_owner_begin, uint64_t n_owners, uint32_t threshold, uint32_t* d_top,
                              uint32_t* d_top_score, uint32_t* d_n_tied, uint64_t out_stride, void* stream);
 
+/* ---- MLST typing: the N best alleles per record and locus, reduced on the device.
+ * The reference's `limit` / `limit_number`: the first 5 items of each locus'
+ * result under "All results" (probabilistic_filter_mlst_model.py:258-259,
+ * 278-282).  N = n_ranks, 1 <= N <= XS_MLST_MAX_RANKS.  All integers:
+ *
+ *   A record probed whole (a hit row of num_docs counts): the docs ordered by
+ *   count descending, then doc index ascending (COBS order); zero counts take
+ *   part.  Rank j < min(N, num_docs) is the j-th doc of that order and its
+ *   count; ranks j >= num_docs are XS_MLST_NONE, 0.  An all-zero row gives docs
+ *   0 .. N-1 with score 0.
+ *   A chunked record (xs_mlst_chunk_rule_t): only alleles with sum > 0 take
+ *   part, ordered by sum descending, then the lower first passing chunk, then
+ *   the higher count in that chunk, then the lower doc (the reference's stable
+ *   sort by -sum over its dict, :248-256); ranks beyond their number are
+ *   XS_MLST_NONE, 0.
+ *
+ * Rank 0 is top / top_score of the calls above; n_tied keeps its meaning. */
+#define XS_MLST_MAX_RANKS 8
+
+/* The row reduction alone (replaces sorting a whole row to cut its first
+ * limit_number items, :278-282), over a device matrix (n x num_docs uint32,
+ * row-major, 4-byte aligned), asynchronous on `stream`.  Rank j of row r is
+ * written at index r * rank_stride + j of d_rank_allele and d_rank_score
+ * (rank_stride >= n_ranks), so one call per locus fills its slice of
+ * n x n_loci x n_ranks arrays (rank_stride = n_loci * n_ranks, pointers offset
+ * by locus * n_ranks).  d_top, d_top_score and d_n_tied (each may be NULL) get
+ * xs_mlst_top_device's values at index r * top_stride, from the same pass. */
+int xs_mlst_ranks_device(const uint32_t* d_hits, uint64_t n, uint64_t num_docs, uint32_t n_ranks, uint32_t* d_top,
+                         uint32_t* d_top_score, uint32_t* d_n_tied, uint64_t top_stride, uint32_t* d_rank_allele,
+                         uint32_t* d_rank_score, uint64_t rank_stride, void* stream);
+
+/* The chunk reduction alone (:248-259) over a device matrix of chunk rows, owners
+ * as xs_mlst_chunk_top_device takes them: rank j of owner o at index
+ * o * rank_stride + j.  An owner without rows gets XS_MLST_NONE, 0 at every
+ * rank.  Returns once they are written. */
+int xs_mlst_chunk_ranks_device(const uint32_t* d_hits, uint64_t n_chunks, uint64_t num_docs,
+                               const uint64_t* d_owner_begin, uint64_t n_owners, uint32_t threshold, uint32_t n_ranks,
+                               uint32_t* d_rank_allele, uint32_t* d_rank_score, uint64_t rank_stride, void* stream);
+
+/* xs_mlst_type_contigs with the ranks (replaces predict(limit=True)'s per-locus
+ * searches, whole rows copied back and sorted on the host, :236-286): short
+ * records, contigs or both in one call, every argument and output of
+ * xs_mlst_type_contigs as there, and rank_allele, rank_score: n x n_loci x
+ * n_ranks uint32, row-major, host memory.  The hit rows and the chunk sums are
+ * reduced to the ranks on the device; 8 * n_ranks more bytes per (record, locus)
+ * go to the host.  XS_ERR_ARG beyond xs_mlst_type_contigs': n_ranks 0 or above
+ * XS_MLST_MAX_RANKS, a NULL rank output with n > 0. */
+int xs_mlst_type_ranked(xs_bank* const* loci, uint32_t n_loci, const uint64_t* locus_width,
+                        const xs_mlst_chunk_rule_t* rule, const char* seqs, const uint64_t* offsets, uint64_t n,
+                        uint32_t step, uint64_t workspace_bytes, uint32_t n_ranks, uint32_t* top, uint32_t* top_score,
+                        uint32_t* n_tied, uint64_t* num_kmers_out, uint32_t* rank_allele, uint32_t* rank_score);
+
+/* The same for reads already in HBM, as xs_mlst_type_contigs_device takes them. */
+int xs_mlst_type_ranked_device(xs_bank* const* loci, uint32_t n_loci, const uint64_t* locus_width,
+                               const xs_mlst_chunk_rule_t* rule, const void* d_seqs, uint64_t seq_bytes,
+                               const uint64_t* d_offsets, const uint64_t* host_offsets, uint64_t n, uint32_t step,
+                               uint64_t workspace_bytes, uint32_t n_ranks, uint32_t* top, uint32_t* top_score,
+                               uint32_t* n_tied, uint64_t* num_kmers_out, uint32_t* rank_allele,
+                               uint32_t* rank_score);
+
 /* Record HIP events around the probe kernel of every query on this handle. */
 int xs_bank_set_profiling(xs_bank* bank, int on);
 /* Duration of the probe kernel of the last profiled query, milliseconds. */

@@ -1,7 +1,7 @@
 """MLST typing over reads at BASELINE config-4 size, the existing path and the
 new one in one run on one GPU:
 
-    python tools/mlst_typing_bench.py [--reads 1000000] [--out FILE] [--time-limit 900]
+    python tools/mlst_typing_bench.py [--reads 1000000] [--ranks N] [--out FILE] [--time-limit 900]
 
 and the assembly leg, ``predict_columnar`` over a FASTA of contigs, on this
 checkout and on another one (the parent commit, built beforehand) in one run:
@@ -26,6 +26,13 @@ query_device into an n x D device matrix), the reduction alone over that matrix
 sizes.  Before timing, legs b and c must agree, and equal numpy's argmax / max /
 count over leg a's rows on a sample of reads.  Prints one JSON line (and writes
 it to --out).  The run ends itself after --time-limit seconds.
+
+With ``--ranks N`` the same run also measures the N best alleles per read and
+locus: ``mlst_type_ranked`` on the reads already in HBM (beside leg c), and the
+ranked reduction alone (7 x mlst_ranks_device between two device events, beside
+the top-1 reduction over the same matrix), with their ratio.  Before timing, the
+ranked call's top / score / tied must equal leg c's, its rank 0 its top, and on
+the sample its ranks the stable argsort of leg a's rows.
 
 The assembly leg writes one synthetic FASTA (--genomes genomes of --genome-mbp
 Mbp each, cut into contigs of 20-500 kbp, 80 columns per line, one allele of
@@ -216,6 +223,7 @@ def main():
     ap.add_argument("--root", type=Path, default=ROOT, help=argparse.SUPPRESS)
     ap.add_argument("--fasta", type=Path, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--reads", type=int, default=1_000_000)
+    ap.add_argument("--ranks", type=int, default=0, help="also measure the N best alleles per read and locus")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--existing-warmup", type=int, default=1, help="leg a (seconds per call at full size)")
@@ -240,7 +248,7 @@ def main():
 
     import torch
     from xspect2_amd import _lib
-    from xspect2_amd.bank import DeviceReads, mlst_top_device, mlst_type
+    from xspect2_amd.bank import DeviceReads, mlst_ranks_device, mlst_top_device, mlst_type, mlst_type_ranked
     from xspect2_amd.packing import pack_fixed
 
     if not torch.cuda.is_available():
@@ -267,17 +275,30 @@ def main():
     got_b = mlst_type(banks, packed)
     got_c = mlst_type(banks, dreads)
     same_bc = all(np.array_equal(x, y) for x, y in zip(got_b, got_c))
-    mismatches = 0
+    N = a.ranks
+    widths = [int(sizes[li, 0]) for li in range(LOCI)]  # the model's "average" size; 150 bp reads are never chunked
+    got_r = mlst_type_ranked(banks, dreads, widths, N) if N else None
+    mismatches = rank_mismatches = 0
     for l, bank in enumerate(banks):
         rows = bank.mlst_query(packed, [], [], 0)[0][sample]
         m = rows.max(axis=1)
         mismatches += int((got_b[0][sample, l] != rows.argmax(axis=1)).sum() + (got_b[1][sample, l] != m).sum()
                           + (got_b[2][sample, l] != (rows == m[:, None]).sum(axis=1)).sum())
+        if N:
+            order = np.argsort(-rows.astype(np.int64), axis=1, kind="stable")[:, :N]
+            rank_mismatches += int((got_r[4][sample, l] != order).sum()
+                                   + (got_r[5][sample, l] != np.take_along_axis(rows, order, axis=1)).sum())
         del rows
     own = (got_b[1].max(axis=1) == READ_LEN - K + 1)  # an error-free window scores all its k-mers somewhere
     checks = {"b_equals_c": bool(same_bc), "sample_reads": int(sample.size), "sample_mismatches_vs_leg_a_rows": mismatches,
               "reads_with_a_full_score": int(own.sum()), "num_kmers_ok": bool((got_b[3] == READ_LEN - K + 1).all())}
     checks["ok"] = bool(same_bc and mismatches == 0 and own.all() and checks["num_kmers_ok"])
+    if N:
+        checks["ranked_equals_c"] = all(np.array_equal(x, y) for x, y in zip(got_c, got_r[:4]))
+        checks["rank0_is_top"] = bool(np.array_equal(got_r[4][:, :, 0], got_r[0]) and np.array_equal(got_r[5][:, :, 0], got_r[1]))
+        checks["sample_rank_mismatches_vs_leg_a_rows"] = rank_mismatches
+        checks["ok"] = bool(checks["ok"] and checks["ranked_equals_c"] and checks["rank0_is_top"] and rank_mismatches == 0)
+    del got_r
 
     # ---- the legs
     def leg_a():
@@ -289,6 +310,9 @@ def main():
         "b_mlst_type_host_reads": timed(lambda: mlst_type(banks, packed), a.warmup, a.repeats, sync),
         "c_mlst_type_device_reads": timed(lambda: mlst_type(banks, dreads), a.warmup, a.repeats, sync),
     }
+    if N:
+        legs["c_mlst_type_ranked_device_reads"] = timed(lambda: mlst_type_ranked(banks, dreads, widths, N), a.warmup,
+                                                        a.repeats, sync)
     sweep = {str(mib): timed(lambda mib=mib: mlst_type(banks, dreads, workspace_bytes=mib << 20), a.warmup,
                              a.repeats, sync) for mib in a.sweep_mib}
 
@@ -308,19 +332,39 @@ def main():
         for l in range(LOCI):
             mlst_top_device(hits, n, ALLELES, outs[0][l:], outs[1][l:], outs[2][l:], LOCI, stream=s)
 
-    for _ in range(a.warmup):
-        reduce_all()
-    sync()
-    ev_ms = []
-    for _ in range(a.repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        reduce_all()
-        e1.record()
+    def by_events(fn):
+        for _ in range(a.warmup):
+            fn()
         sync()
-        ev_ms.append(e0.elapsed_time(e1))
+        ms = []
+        for _ in range(a.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            sync()
+            ms.append(e0.elapsed_time(e1))
+        return ms
+
+    ev_ms = by_events(reduce_all)
     reduce_ms = statistics.median(ev_ms)
     matrix_gb = LOCI * n * ALLELES * 4 / 1e9
+    ranked = None
+    if N:
+        r_outs = [torch.empty(n * LOCI * N, dtype=torch.int32, device=dev) for _ in range(2)]  # n x LOCI x N
+
+        def reduce_ranked():
+            for l in range(LOCI):
+                mlst_ranks_device(hits, n, ALLELES, N, r_outs[0][l * N:], r_outs[1][l * N:], LOCI * N, outs[0][l:],
+                                  outs[1][l:], outs[2][l:], LOCI, stream=s)
+
+        r_ms = by_events(reduce_ranked)
+        ranked_ms = statistics.median(r_ms)
+        ranked = {"ranks": N, "median_ms": round(ranked_ms, 3), "ms": [round(x, 3) for x in r_ms],
+                  "matrix_gb_read": round(matrix_gb, 2), "rank_mb_written": round(LOCI * n * N * 8 / 1e6, 1),
+                  "gb_per_s": round(matrix_gb / ranked_ms * 1e3, 1),
+                  "over_top1_reduction": round(ranked_ms / reduce_ms, 2),
+                  "clock": "device events around 7 x mlst_ranks_device (top, score, tied and the ranks) over the same matrix"}
 
     med = {k: v["median_ms"] for k, v in legs.items()}
     line = {
@@ -334,6 +378,9 @@ def main():
                             "matrix_gb_read": round(matrix_gb, 2), "gb_per_s": round(matrix_gb / reduce_ms * 1e3, 1),
                             "clock": "device events around 7 x mlst_top_device over the n x D device matrix"},
         "c_over_probe_step": round(med["c_mlst_type_device_reads"] / probe["median_ms"], 2),
+        **({"ranked_reduction_alone": ranked,
+            "ranked_over_c": round(med["c_mlst_type_ranked_device_reads"] / med["c_mlst_type_device_reads"], 2)}
+           if N else {}),
         "c_workspace_sweep_mib": sweep,
         "clock": "host perf_counter around calls that return synchronised (legs), a device synchronise (probe step)",
     }

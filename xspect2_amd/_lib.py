@@ -31,6 +31,7 @@ XS_PATH_PARTITIONED = 1
 
 XS_BEST_AMBIGUOUS = 0xFFFFFFFF
 XS_MLST_NONE = 0xFFFFFFFF
+XS_MLST_MAX_RANKS = 8
 
 XS_FASTX_FASTA = 1
 XS_FASTX_FASTQ = 2
@@ -166,6 +167,12 @@ SIGNATURES = {
     "xs_mlst_split_size": (_int, [_vp, _u64, _u64, _u32, _vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "xs_mlst_split_device": (_int, [_vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "xs_mlst_chunk_top_device": (_int, [_vp, _u64, _u64, _vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp]),
+    "xs_mlst_ranks_device": (_int, [_vp, _u64, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "xs_mlst_chunk_ranks_device": (_int, [_vp, _u64, _u64, _vp, _u64, _u32, _u32, _vp, _vp, _u64, _vp]),
+    "xs_mlst_type_ranked": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _u64, _u32, _u64, _u32, _vp, _vp, _vp, _vp, _vp,
+                                   _vp]),
+    "xs_mlst_type_ranked_device": (_int, [_vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _u32, _vp, _vp,
+                                          _vp, _vp, _vp, _vp]),
     "xs_bank_set_profiling": (_int, [_vp, _int]),
     "xs_bank_last_probe_ms": (_int, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "xs_bank_probe_stats": (_int, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double),

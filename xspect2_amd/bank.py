@@ -599,16 +599,8 @@ def _chunk_rule(rule):
     return _lib.MlstChunkRule(int(long_len), int(scale10), int(scale100), int(threshold), 0)
 
 
-def mlst_type_contigs(banks: Sequence[Bank], reads, widths, step: int = 1, workspace_bytes: int = 0, rule=None):
-    """xs_mlst_type_contigs: short reads, contigs or both typed against every locus
-    bank in one call.  Records below the rule's long_len (10 kbp) follow
-    ``mlst_type``; longer ones are cut on the device into the reference's
-    overlapping chunks per locus (widths[l]: the locus' base width, the model's
-    ``avg_locus_bp_size``), the chunks probed there, their counts above the
-    threshold summed per allele and reduced to the top allele (XS_MLST_NONE, 0, 0
-    where no chunk passes).  Same kinds of ``reads`` and the same four arrays as
-    ``mlst_type``; num_kmers is the whole record's count.  rule: None, a
-    ``_lib.MlstChunkRule`` or (long_len, scale10_len, scale100_len, threshold)."""
+def _type_contigs(banks: Sequence[Bank], reads, widths, step: int, workspace_bytes: int, rule, ranks: int):
+    """xs_mlst_type_contigs / _device (ranks == 0) or xs_mlst_type_ranked / _device."""
     banks = list(banks)
     if step < 1:
         raise ValueError("step must be >= 1")
@@ -625,18 +617,77 @@ def mlst_type_contigs(banks: Sequence[Bank], reads, widths, step: int = 1, works
     handles = (ctypes.c_void_p * max(L, 1))(*[b.handle.value for b in banks])
     top, score, tied = (_HOST_POOL.empty((n, L), np.uint32) for _ in range(3))
     nk = np.empty(n, dtype=np.uint64)
-    outs = (_ptr(top) or None, _ptr(score) or None, _ptr(tied) or None, _ptr(nk) or None)
+    res = (top, score, tied, nk)
+    outs = tuple(_ptr(a) or None for a in res)
+    if ranks:
+        rank_arrays = tuple(_HOST_POOL.empty((n, L, ranks), np.uint32) for _ in range(2))
+        outs = (ranks,) + outs + tuple(_ptr(a) or None for a in rank_arrays)
+        res += rank_arrays
+    lib = load()
     if dev:
         ho = getattr(reads, "host_offsets", None)
         if ho is None and hasattr(reads, "offsets"):  # a device reader batch keeps its offsets on the host too
             ho = np.ascontiguousarray(reads.offsets, dtype=np.uint64)
-        check(load().xs_mlst_type_contigs_device(handles, L, _ptr(w), rule_p, pr.seqs_ptr or None, pr.seq_bytes,
-                                                 pr.offsets_ptr or None, _ptr(ho) if ho is not None else None, n,
-                                                 step, workspace_bytes, *outs))
+        fn = lib.xs_mlst_type_ranked_device if ranks else lib.xs_mlst_type_contigs_device
+        check(fn(handles, L, _ptr(w), rule_p, pr.seqs_ptr or None, pr.seq_bytes, pr.offsets_ptr or None,
+                 _ptr(ho) if ho is not None else None, n, step, workspace_bytes, *outs))
     else:
-        check(load().xs_mlst_type_contigs(handles, L, _ptr(w), rule_p, _ptr(pr.buf) or None, _ptr(pr.offsets), n,
-                                          step, workspace_bytes, *outs))
-    return top, score, tied, nk
+        fn = lib.xs_mlst_type_ranked if ranks else lib.xs_mlst_type_contigs
+        check(fn(handles, L, _ptr(w), rule_p, _ptr(pr.buf) or None, _ptr(pr.offsets), n, step, workspace_bytes, *outs))
+    return res
+
+
+def mlst_type_contigs(banks: Sequence[Bank], reads, widths, step: int = 1, workspace_bytes: int = 0, rule=None):
+    """xs_mlst_type_contigs: short reads, contigs or both typed against every locus
+    bank in one call.  Records below the rule's long_len (10 kbp) follow
+    ``mlst_type``; longer ones are cut on the device into the reference's
+    overlapping chunks per locus (widths[l]: the locus' base width, the model's
+    ``avg_locus_bp_size``), the chunks probed there, their counts above the
+    threshold summed per allele and reduced to the top allele (XS_MLST_NONE, 0, 0
+    where no chunk passes).  Same kinds of ``reads`` and the same four arrays as
+    ``mlst_type``; num_kmers is the whole record's count.  rule: None, a
+    ``_lib.MlstChunkRule`` or (long_len, scale10_len, scale100_len, threshold)."""
+    return _type_contigs(banks, reads, widths, step, workspace_bytes, rule, 0)
+
+
+def mlst_type_ranked(banks: Sequence[Bank], reads, widths, ranks: int, step: int = 1, workspace_bytes: int = 0,
+                     rule=None):
+    """xs_mlst_type_ranked: ``mlst_type_contigs`` with the ``ranks`` (1 ..
+    XS_MLST_MAX_RANKS) best alleles per record and locus, the reference's
+    ``limit`` / ``limit_number``.  Returns (top, top_score, n_tied, num_kmers,
+    rank_allele, rank_score); the last two are [n, len(banks), ranks] uint32.  A
+    record probed whole ranks every doc by count descending, then doc index
+    (zero counts too); a chunked record only the alleles with a sum > 0, in the
+    order of the reference's stable sort; ranks beyond them are XS_MLST_NONE, 0.
+    Rank 0 is (top, top_score).  The hit rows and chunk sums are reduced on the
+    device."""
+    ranks = int(ranks)
+    if not 1 <= ranks <= _lib.XS_MLST_MAX_RANKS:
+        raise ValueError(f"ranks must be in 1 .. {_lib.XS_MLST_MAX_RANKS}")
+    return _type_contigs(banks, reads, widths, step, workspace_bytes, rule, ranks)
+
+
+def mlst_ranks_device(hits, n: int, num_docs: int, ranks: int, rank_allele, rank_score, rank_stride: int | None = None,
+                      top=None, top_score=None, n_tied=None, top_stride: int = 1, stream: int | None = None) -> None:
+    """xs_mlst_ranks_device: per row of a device hit matrix (n x num_docs uint32) its
+    ``ranks`` best docs (count descending, then doc index) and their counts, rank j
+    of row r at index r * rank_stride + j (rank_stride: ``ranks`` by default); top,
+    top_score, n_tied (each optional) as ``mlst_top_device`` writes them, from the
+    same pass."""
+    check(load().xs_mlst_ranks_device(_dptr(hits), n, num_docs, ranks, _dptr(top), _dptr(top_score), _dptr(n_tied),
+                                      top_stride, _dptr(rank_allele), _dptr(rank_score),
+                                      ranks if rank_stride is None else rank_stride, stream))
+
+
+def mlst_chunk_ranks_device(hits, n_chunks: int, num_docs: int, owner_begin, n_owners: int, threshold: int,
+                            ranks: int, rank_allele, rank_score, rank_stride: int | None = None,
+                            stream: int | None = None) -> None:
+    """xs_mlst_chunk_ranks_device: per owner of rows [owner_begin[o], owner_begin[o + 1])
+    of a device matrix of chunk rows, the ``ranks`` best alleles of the summed
+    counts above `threshold` and their sums, rank j at index o * rank_stride + j."""
+    check(load().xs_mlst_chunk_ranks_device(_dptr(hits), n_chunks, num_docs, _dptr(owner_begin), n_owners, threshold,
+                                            ranks, _dptr(rank_allele), _dptr(rank_score),
+                                            ranks if rank_stride is None else rank_stride, stream))
 
 
 def mlst_split_size(lengths, width: int, k: int, rule=None) -> tuple[int, int]:
@@ -691,5 +742,6 @@ def _dptr(x) -> int | None:
 
 
 __all__ = ["Bank", "bloom_parameters", "cobs_signature_size", "KIND_NAMES", "pinned_empty", "max_kmers", "probe_kernel_names",
-           "mlst_top_device", "mlst_type", "mlst_type_contigs", "mlst_split_size", "mlst_split_device",
+           "mlst_top_device", "mlst_type", "mlst_type_contigs", "mlst_type_ranked", "mlst_ranks_device",
+           "mlst_chunk_ranks_device", "mlst_split_size", "mlst_split_device",
            "mlst_chunk_top_device", "DeviceReads", "XS_BANK_COBS_CLASSIC", "XS_BANK_COBS_COMPACT", "XS_BANK_RBLOOM", "_lib"]

@@ -161,8 +161,8 @@ struct xs_bank {
     xs::DevBuf small_d;
     // MLST typing of contigs (mlst_contigs_run in xs_mlst.cpp): a range's chunk texts, their offsets and
     // accumulators, the call's chunk runs, and for a batch of many short runs the compacted short reads with
-    // their index and outputs
-    xs::DevBuf mc_text, mc_offs, mc_sum, mc_key, mc_runs, mc_short, mc_idx, mc_out;
+    // their index and outputs; a ranked call's n x loci x N rank arrays
+    xs::DevBuf mc_text, mc_offs, mc_sum, mc_key, mc_runs, mc_short, mc_idx, mc_out, mc_ranks;
     xs::PinnedBuf mc_runs_h, mc_idx_h;
     hipEvent_t hstage_ev[2] = {nullptr, nullptr};
     hipStream_t copy_stream = nullptr, d2h_stream = nullptr;
@@ -184,7 +184,7 @@ struct xs_bank {
         for (xs::DevBuf* d : {&seqs, &offs, &nseg, &unit_ofs, &unit_read, &n_units, &scan_tmp, &nk, &hits, &partials,
                               &totals, &tmp, &best, &narrow, &ovf, &rows_read, &pk_nkc, &pk_kofs, &pk_scan, &pk_entries,
                               &pk_tbl, &pk_miss, &pk_aux, &bloom_tot, &mc_text, &mc_offs, &mc_sum, &mc_key, &mc_runs,
-                              &mc_short, &mc_idx, &mc_out}) {
+                              &mc_short, &mc_idx, &mc_out, &mc_ranks}) {
             d->guard_ev = &ws_ev;
             d->guard_used = &ws_used;
             d->acct = &ws_acct;

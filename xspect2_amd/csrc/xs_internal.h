@@ -321,6 +321,22 @@ hipError_t launch_mlst_scatter_rows(const uint32_t* index, uint64_t m, uint64_t 
                                     const uint32_t* src1, const uint32_t* src2, uint32_t* dst0, uint32_t* dst1,
                                     uint32_t* dst2, hipStream_t s);
 
+// ---- the N best alleles per row / owner (xs_mlst_ranks.hip), 1 <= n_ranks <= kMlstMaxRanks --------
+// Per row of an n x D matrix: rank j < min(n_ranks, D) = the j-th doc by count descending, then doc
+// ascending, and its count; ranks from D on: kMlstNone, 0.  Rank j of row r goes to
+// rank_*[r * rank_stride + j].  top / top_score / n_tied (each may be null) as launch_mlst_top
+// writes them at top_stride, from the same pass over the row.
+constexpr uint32_t kMlstMaxRanks = 8;  // = XS_MLST_MAX_RANKS (xs_mlst.cpp asserts it)
+hipError_t launch_mlst_ranks(const uint32_t* hits, uint64_t n, uint64_t D, uint32_t n_ranks, uint32_t* top,
+                             uint32_t* top_score, uint32_t* n_tied, uint64_t top_stride, uint32_t* rank_allele,
+                             uint32_t* rank_score, uint64_t rank_stride, hipStream_t s);
+// Per owner row of D (sum, key): the docs with a sum > 0 by sum descending, then key ascending, then
+// doc ascending (launch_mlst_owner_top's order); ranks beyond them: kMlstNone, 0.  Owner o writes at
+// rank_*[row * rank_stride + j], row = rec ? rec[o * rec_stride] : o.
+hipError_t launch_mlst_owner_ranks(const unsigned long long* sum, const unsigned long long* key, uint64_t n_owners,
+                                   uint64_t D, const uint64_t* rec, uint32_t rec_stride, uint32_t n_ranks,
+                                   uint32_t* rank_allele, uint32_t* rank_score, uint64_t rank_stride, hipStream_t s);
+
 // dst[i] = src[i] as uint8 (hit_bytes 1) or uint16 (2); the caller guarantees the values fit.
 hipError_t launch_narrow_hits(const uint32_t* src, void* dst, uint64_t n, int hit_bytes, hipStream_t s,
                               uint32_t* overflow = nullptr);

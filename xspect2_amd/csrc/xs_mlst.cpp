@@ -1,5 +1,6 @@
 // xs_mlst.cpp — the MLST entry points of the C ABI: chunk sums (xs_mlst_sum, xs_mlst_query), typing of
-// reads (xs_mlst_type*) and of contigs (xs_mlst_type_contigs*), and the splitter's pieces on their own.
+// reads (xs_mlst_type*) and of contigs (xs_mlst_type_contigs*, with the N best alleles xs_mlst_type_ranked*),
+// and the splitter's and the reductions' pieces on their own.
 // The probes are xs_query.cpp's (xs_query.h); the host's plan of a contig call is xs_mlst_plan.h.
 #include "xs_mlst_plan.h"
 #include "xs_query.h"
@@ -21,6 +22,16 @@ constexpr size_t kDirectRingMin = 64u << 20;  // xs_mlst_query's direct rows
 struct MlstTypeOut {
     uint32_t *top, *top_score, *n_tied;  // n x loci each, host (n_tied may be null)
     uint64_t* num_kmers;                 // n, host (may be null)
+    uint32_t n_ranks = 0;                // > 0: the ranked call (xs_mlst_type_ranked)
+    uint32_t *rank_allele = nullptr, *rank_score = nullptr;  // n x loci x n_ranks each, host
+};
+static_assert(kMlstMaxRanks == XS_MLST_MAX_RANKS, "the kernels' cap and the header's");
+
+// Where a span's ranks go on the device: rank j of (record r, locus l) at [(r * loci + l) * N + j].  N == 0: no ranks.
+struct RankBufs {
+    uint32_t N = 0;
+    uint32_t *allele = nullptr, *score = nullptr;
+    RankBufs at(uint64_t cell) const { return N ? RankBufs{N, allele + cell * N, score + cell * N} : RankBufs{}; }
 };
 
 // The argument errors of xs_mlst_type / xs_mlst_type_device that need no device.
@@ -38,6 +49,14 @@ int mlst_type_check(xs_bank* const* loci, uint32_t n_loci, uint64_t n, uint32_t 
         if (loci[l]->device != loci[0]->device) return fail(XS_ERR_ARG, "locus %u is on another device than locus 0", l);
         if (loci[l]->k != loci[0]->k) return fail(XS_ERR_ARG, "locus %u has another k than locus 0", l);
     }
+    return XS_OK;
+}
+
+// The ranked calls' own argument errors.
+int mlst_ranks_check(uint64_t n, const MlstTypeOut& out) {
+    if (out.n_ranks == 0 || out.n_ranks > kMlstMaxRanks)
+        return fail(XS_ERR_ARG, "n_ranks must be in 1 .. %u", kMlstMaxRanks);
+    if (n && (!out.rank_allele || !out.rank_score)) return fail(XS_ERR_ARG, "null argument (rank outputs)");
     return XS_OK;
 }
 
@@ -81,11 +100,12 @@ struct TypeCall {
 
 // The device outputs of a typing call, in the first locus' buffers: the rows one probe fills (row_cap
 // rows of the widest locus within the workspace), top / score / tied (n x loci each) and, when the
-// caller wants them, the reads' k-mer counts.
+// caller wants them, the reads' k-mer counts; a ranked call's ranks (n x loci x N twice) in mc_ranks.
 struct TypeBufs {
     uint64_t n, L, dmax = 1, ws, row_cap;
     uint32_t *rows = nullptr, *top = nullptr, *score = nullptr, *tied = nullptr;
     uint64_t* nk = nullptr;
+    RankBufs ranks;
     TypeBufs(xs_bank* const* loci, uint32_t n_loci, uint64_t n_, uint64_t workspace_bytes)
         : n(n_), L(n_loci), ws(workspace_bytes ? workspace_bytes : kMlstTypeWs) {
         for (uint32_t l = 0; l < n_loci; ++l) dmax = std::max(dmax, loci[l]->D);
@@ -100,24 +120,33 @@ struct TypeBufs {
         score = top + n * L;
         tied = out.n_tied ? score + n * L : nullptr;
         nk = out.num_kmers ? b0->nk.as<uint64_t>() : nullptr;
+        if (out.n_ranks) {
+            const uint64_t cells = n * L * out.n_ranks;
+            if (int rc = b0->mc_ranks.ensure(cells * 4 * 2)) return rc;
+            ranks = RankBufs{out.n_ranks, b0->mc_ranks.as<uint32_t>(), b0->mc_ranks.as<uint32_t>() + cells};
+        }
         return XS_OK;
     }
     int to_host(xs_bank* b0, const MlstTypeOut& out, hipStream_t s) const {
-        const D2hPart parts[4] = {{out.top, top, n * L * 4},
+        const size_t rank_bytes = n * L * ranks.N * 4;
+        const D2hPart parts[6] = {{out.top, top, n * L * 4},
                                   {out.top_score, score, n * L * 4},
                                   {out.n_tied, tied, tied ? n * L * 4 : 0},
-                                  {out.num_kmers, nk, nk ? n * 8 : 0}};
-        return d2h_parts(b0, parts, 4, kTypeRingMin, s);
+                                  {out.num_kmers, nk, nk ? n * 8 : 0},
+                                  {out.rank_allele, ranks.allele, rank_bytes},
+                                  {out.rank_score, ranks.score, rank_bytes}};
+        return d2h_parts(b0, parts, 6, kTypeRingMin, s);
     }
 };
 
 // n reads [r0, r0 + n) probed against every locus in pieces of `per` reads, each piece's rows reduced into
 // columns of the outputs whose row 0 is the first read's (top / score / tied, and nk when wanted, point at
 // it).  ho: the reads' offsets on the host ([0] = 0), or null: a piece's plans then take the batch's
-// bytes, an upper bound, for its own.  The first locus' probe computes the k-mer counts.
+// bytes, an upper bound, for its own.  The first locus' probe computes the k-mer counts.  ranks (its
+// pointers at the first read's too): the ranked row kernel reduces each piece in place of the top kernel.
 int mlst_type_span(xs_bank* const* loci, uint32_t n_loci, const Inputs& all, const uint64_t* ho, uint64_t r0, uint64_t n,
                    uint64_t per, uint32_t step, uint32_t* d_rows, uint32_t* top, uint32_t* score, uint32_t* tied,
-                   uint64_t* nk, hipStream_t s) {
+                   uint64_t* nk, const RankBufs& ranks, hipStream_t s) {
     const uint64_t L = n_loci;
     for (uint64_t a = 0; a < n; a += per) {
         const uint64_t cn = std::min(per, n - a);
@@ -125,7 +154,13 @@ int mlst_type_span(xs_bank* const* loci, uint32_t n_loci, const Inputs& all, con
         for (uint32_t l = 0; l < n_loci; ++l) {
             if (int rc = run_query(loci[l], in, step, d_rows, l == 0 && nk ? nk + a : nullptr, nullptr, s)) return rc;
             const uint64_t o = a * L + l;
-            HIPCHK(launch_mlst_top(d_rows, cn, loci[l]->D, top + o, score + o, tied ? tied + o : nullptr, L, s));
+            if (ranks.N) {
+                const RankBufs rk = ranks.at(o);
+                HIPCHK(launch_mlst_ranks(d_rows, cn, loci[l]->D, rk.N, top + o, score + o, tied ? tied + o : nullptr, L,
+                                         rk.allele, rk.score, L * rk.N, s));
+            } else {
+                HIPCHK(launch_mlst_top(d_rows, cn, loci[l]->D, top + o, score + o, tied ? tied + o : nullptr, L, s));
+            }
         }
     }
     return XS_OK;
@@ -141,7 +176,8 @@ int mlst_type_run(xs_bank* const* loci, uint32_t n_loci, const Inputs& all, cons
     const uint64_t per = std::min(o.row_cap, all.n);
     if (int rc = ws_enter(b0, s)) return rc;
     if (int rc = o.reserve(b0, per, out)) return rc;
-    if (int rc = mlst_type_span(loci, n_loci, all, host_offs, 0, o.n, per, step, o.rows, o.top, o.score, o.tied, o.nk, s))
+    if (int rc = mlst_type_span(loci, n_loci, all, host_offs, 0, o.n, per, step, o.rows, o.top, o.score, o.tied, o.nk,
+                                RankBufs{}, s))
         return rc;
     if (int rc = ws_leave(b0, s)) return rc;
     return o.to_host(b0, out, s);
@@ -183,7 +219,8 @@ int type_short_in_place(const ContigCall& c, const RecordKinds& kinds, const Typ
     for (const auto& run : kinds.short_runs) {
         const uint64_t at = run.first * o.L;
         if (int rc = mlst_type_span(c.loci, c.n_loci, c.all, c.ho, run.first, run.second - run.first, o.row_cap, c.step,
-                                    o.rows, o.top + at, o.score + at, o.tied ? o.tied + at : nullptr, nullptr, c.s))
+                                    o.rows, o.top + at, o.score + at, o.tied ? o.tied + at : nullptr, nullptr,
+                                    o.ranks.at(at), c.s))
             return rc;
     }
     return XS_OK;
@@ -193,12 +230,12 @@ int type_short_in_place(const ContigCall& c, const RecordKinds& kinds, const Typ
 int type_short_compacted(const ContigCall& c, const RecordKinds& kinds, const TypeBufs& o) {
     xs_bank* b0 = c.loci[0];
     const hipStream_t s = c.s;
-    const uint64_t m = kinds.n_short, L = o.L;
+    const uint64_t m = kinds.n_short, L = o.L, N = o.ranks.N;
     if (m >= (1ull << 32)) return fail(XS_ERR_ARG, "at most 2^32-1 short records per call");
     if (int rc = b0->mc_idx_h.ensure((m + 1) * 8 + m * 4)) return rc;
     if (int rc = b0->mc_idx.ensure((m + 1) * 8 + m * 4)) return rc;
     if (int rc = b0->mc_short.ensure(kinds.short_bytes + kPad)) return rc;
-    if (int rc = b0->mc_out.ensure(m * L * 4 * 3)) return rc;
+    if (int rc = b0->mc_out.ensure(m * L * 4 * (3 + 2 * N))) return rc;
     uint64_t* co = static_cast<uint64_t*>(b0->mc_idx_h.p);  // the compacted reads' m + 1 offsets, then their indices
     uint32_t* ci = reinterpret_cast<uint32_t*>(co + m + 1);
     uint64_t j = 0, ob = 0;
@@ -217,11 +254,15 @@ int type_short_compacted(const ContigCall& c, const RecordKinds& kinds, const Ty
     uint32_t* c_top = b0->mc_out.as<uint32_t>();
     uint32_t* c_score = c_top + m * L;
     uint32_t* c_tied = o.tied ? c_score + m * L : nullptr;
+    const RankBufs c_ranks = N ? RankBufs{o.ranks.N, c_top + 3 * m * L, c_top + (3 + N) * m * L} : RankBufs{};
     const Inputs shorts{b0->mc_short.as<uint8_t>(), kinds.short_bytes, d_co, m};
     if (int rc = mlst_type_span(c.loci, c.n_loci, shorts, co, 0, m, o.row_cap, c.step, o.rows, c_top, c_score, c_tied,
-                                nullptr, s))
+                                nullptr, c_ranks, s))
         return rc;
     HIPCHK(launch_mlst_scatter_rows(d_ci, m, L, c_top, c_score, c_tied, o.top, o.score, o.tied, s));
+    if (N)
+        HIPCHK(launch_mlst_scatter_rows(d_ci, m, L * N, c_ranks.allele, c_ranks.score, nullptr, o.ranks.allele,
+                                        o.ranks.score, nullptr, s));
     return XS_OK;
 }
 
@@ -261,6 +302,11 @@ int type_long_ranges(const ContigCall& c, const ContigPlan& plan, uint32_t thres
             const uint64_t done = g.n_runs - (g.carry_out ? 1 : 0);
             HIPCHK(launch_mlst_owner_top(sum, key, done, D, &d_runs->rec, kMlstRunWords, o.top + l, o.score + l,
                                          o.tied ? o.tied + l : nullptr, o.L, s));
+            if (o.ranks.N) {
+                const RankBufs rk = o.ranks.at(l);
+                HIPCHK(launch_mlst_owner_ranks(sum, key, done, D, &d_runs->rec, kMlstRunWords, rk.N, rk.allele, rk.score,
+                                               o.L * rk.N, s));
+            }
             if (g.carry_out && done > 0) {
                 HIPCHK(hipMemcpyAsync(sum, sum + done * D, D * 8, hipMemcpyDeviceToDevice, s));
                 HIPCHK(hipMemcpyAsync(key, key + done * D, D * 8, hipMemcpyDeviceToDevice, s));
@@ -307,6 +353,65 @@ int mlst_contigs_run(xs_bank* const* loci, uint32_t n_loci, const uint64_t* widt
         if (int rc = type_long_ranges(c, plan, rule.threshold, o)) return rc;
     if (int rc = ws_leave(b0, c.s)) return rc;
     return o.to_host(b0, out, c.s);
+}
+
+// The (sum, key) accumulators of the chunk reductions alone (xs_mlst_chunk_top_device, xs_mlst_chunk_ranks_device):
+// they live for the call only, which returns once its outputs are written.
+struct OwnerAcc {
+    DevBuf buf;
+    unsigned long long *sum = nullptr, *key = nullptr;
+    int fill(const uint32_t* d_hits, uint64_t n_chunks, uint64_t D, const uint64_t* d_owner_begin, uint64_t n_owners,
+             uint32_t threshold, hipStream_t s) {
+        const uint64_t cells = n_owners * D;
+        if (int rc = buf.ensure(cells * 16)) return rc;
+        sum = buf.as<unsigned long long>();
+        key = sum + cells;
+        HIPCHK(hipMemsetAsync(sum, 0, cells * 8, s));
+        HIPCHK(hipMemsetAsync(key, 0xFF, cells * 8, s));
+        HIPCHK(launch_mlst_chunk_acc(d_hits, n_chunks, D, d_owner_begin, 1, n_owners, threshold, 0, sum, key, s));
+        return XS_OK;
+    }
+};
+
+// xs_mlst_type_contigs and xs_mlst_type_ranked, from host reads.
+int contigs_host(xs_bank* const* loci, uint32_t n_loci, const uint64_t* locus_width, const xs_mlst_chunk_rule_t* rule,
+                 const char* seqs, const uint64_t* offsets, uint64_t n, uint32_t step, uint64_t workspace_bytes,
+                 const MlstTypeOut& out) {
+    if (!offsets || (!seqs && n)) return fail(XS_ERR_ARG, "null argument");
+    xs_mlst_chunk_rule_t r;
+    if (int rc = mlst_contigs_check(loci, n_loci, locus_width, rule, offsets[n] - offsets[0], n, step, out, &r)) return rc;
+    TypeCall call;
+    if (int rc = call.lock(loci, n_loci)) return rc;
+    if (n == 0) return XS_OK;
+    Inputs in;
+    if (int rc = call.upload(loci[0], seqs, offsets, n, &in)) return rc;
+    return mlst_contigs_run(loci, n_loci, locus_width, r, in, static_cast<const uint64_t*>(loci[0]->offs_h.p), step,
+                            workspace_bytes, out);
+}
+
+// The same from reads already in HBM.
+int contigs_device(xs_bank* const* loci, uint32_t n_loci, const uint64_t* locus_width, const xs_mlst_chunk_rule_t* rule,
+                   const void* d_seqs, uint64_t seq_bytes, const uint64_t* d_offsets, const uint64_t* host_offsets,
+                   uint64_t n, uint32_t step, uint64_t workspace_bytes, const MlstTypeOut& out) {
+    if (n && (!d_seqs || !d_offsets)) return fail(XS_ERR_ARG, "null argument");
+    xs_mlst_chunk_rule_t r;
+    if (int rc = mlst_contigs_check(loci, n_loci, locus_width, rule, seq_bytes, n, step, out, &r)) return rc;
+    TypeCall call;
+    if (int rc = call.lock(loci, n_loci)) return rc;
+    if (n == 0) return XS_OK;
+    call.drain.s = loci[0]->stream;
+    std::vector<uint64_t> copied;
+    if (!host_offsets) {  // the lengths decide the chunk geometry: one copy back
+        copied.resize(n + 1);
+        HIPCHK(hipMemcpy(copied.data(), d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost));
+        host_offsets = copied.data();
+    }
+    for (uint64_t i = 0; i < n; ++i)
+        if (host_offsets[i + 1] < host_offsets[i]) return bad_offsets();
+    if (host_offsets[0] != 0 || host_offsets[n] > seq_bytes)
+        return fail(XS_ERR_ARG, "offsets must start at 0 and end within seq_bytes");
+    const Inputs in{static_cast<const uint8_t*>(d_seqs), seq_bytes, d_offsets, n};
+    return mlst_contigs_run(loci, n_loci, locus_width, r, in, host_offsets, step, workspace_bytes, out);
 }
 
 }  // namespace
@@ -449,17 +554,7 @@ int xs_mlst_type_contigs(xs_bank* const* loci, uint32_t n_loci, const uint64_t* 
                          uint64_t* num_kmers_out) {
     return xs::guard([&]() -> int {
         const MlstTypeOut out{top, top_score, n_tied, num_kmers_out};
-        if (!offsets || (!seqs && n)) return fail(XS_ERR_ARG, "null argument");
-        xs_mlst_chunk_rule_t r;
-        if (int rc = mlst_contigs_check(loci, n_loci, locus_width, rule, offsets[n] - offsets[0], n, step, out, &r))
-            return rc;
-        TypeCall call;
-        if (int rc = call.lock(loci, n_loci)) return rc;
-        if (n == 0) return XS_OK;
-        Inputs in;
-        if (int rc = call.upload(loci[0], seqs, offsets, n, &in)) return rc;
-        return mlst_contigs_run(loci, n_loci, locus_width, r, in, static_cast<const uint64_t*>(loci[0]->offs_h.p), step,
-                                workspace_bytes, out);
+        return contigs_host(loci, n_loci, locus_width, rule, seqs, offsets, n, step, workspace_bytes, out);
     });
 }
 
@@ -470,25 +565,33 @@ int xs_mlst_type_contigs_device(xs_bank* const* loci, uint32_t n_loci, const uin
                                 uint64_t* num_kmers_out) {
     return xs::guard([&]() -> int {
         const MlstTypeOut out{top, top_score, n_tied, num_kmers_out};
-        if (n && (!d_seqs || !d_offsets)) return fail(XS_ERR_ARG, "null argument");
-        xs_mlst_chunk_rule_t r;
-        if (int rc = mlst_contigs_check(loci, n_loci, locus_width, rule, seq_bytes, n, step, out, &r)) return rc;
-        TypeCall call;
-        if (int rc = call.lock(loci, n_loci)) return rc;
-        if (n == 0) return XS_OK;
-        call.drain.s = loci[0]->stream;
-        std::vector<uint64_t> copied;
-        if (!host_offsets) {  // the lengths decide the chunk geometry: one copy back
-            copied.resize(n + 1);
-            HIPCHK(hipMemcpy(copied.data(), d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost));
-            host_offsets = copied.data();
-        }
-        for (uint64_t i = 0; i < n; ++i)
-            if (host_offsets[i + 1] < host_offsets[i]) return bad_offsets();
-        if (host_offsets[0] != 0 || host_offsets[n] > seq_bytes)
-            return fail(XS_ERR_ARG, "offsets must start at 0 and end within seq_bytes");
-        const Inputs in{static_cast<const uint8_t*>(d_seqs), seq_bytes, d_offsets, n};
-        return mlst_contigs_run(loci, n_loci, locus_width, r, in, host_offsets, step, workspace_bytes, out);
+        return contigs_device(loci, n_loci, locus_width, rule, d_seqs, seq_bytes, d_offsets, host_offsets, n, step,
+                              workspace_bytes, out);
+    });
+}
+
+int xs_mlst_type_ranked(xs_bank* const* loci, uint32_t n_loci, const uint64_t* locus_width,
+                        const xs_mlst_chunk_rule_t* rule, const char* seqs, const uint64_t* offsets, uint64_t n,
+                        uint32_t step, uint64_t workspace_bytes, uint32_t n_ranks, uint32_t* top, uint32_t* top_score,
+                        uint32_t* n_tied, uint64_t* num_kmers_out, uint32_t* rank_allele, uint32_t* rank_score) {
+    return xs::guard([&]() -> int {
+        const MlstTypeOut out{top, top_score, n_tied, num_kmers_out, n_ranks, rank_allele, rank_score};
+        if (int rc = mlst_ranks_check(n, out)) return rc;
+        return contigs_host(loci, n_loci, locus_width, rule, seqs, offsets, n, step, workspace_bytes, out);
+    });
+}
+
+int xs_mlst_type_ranked_device(xs_bank* const* loci, uint32_t n_loci, const uint64_t* locus_width,
+                               const xs_mlst_chunk_rule_t* rule, const void* d_seqs, uint64_t seq_bytes,
+                               const uint64_t* d_offsets, const uint64_t* host_offsets, uint64_t n, uint32_t step,
+                               uint64_t workspace_bytes, uint32_t n_ranks, uint32_t* top, uint32_t* top_score,
+                               uint32_t* n_tied, uint64_t* num_kmers_out, uint32_t* rank_allele,
+                               uint32_t* rank_score) {
+    return xs::guard([&]() -> int {
+        const MlstTypeOut out{top, top_score, n_tied, num_kmers_out, n_ranks, rank_allele, rank_score};
+        if (int rc = mlst_ranks_check(n, out)) return rc;
+        return contigs_device(loci, n_loci, locus_width, rule, d_seqs, seq_bytes, d_offsets, host_offsets, n, step,
+                              workspace_bytes, out);
     });
 }
 
@@ -546,17 +649,46 @@ int xs_mlst_chunk_top_device(const uint32_t* d_hits, uint64_t n_chunks, uint64_t
         if (n_chunks >= (1ull << 32)) return fail(XS_ERR_ARG, "at most 2^32-1 chunks per call");
         if (n_owners == 0) return XS_OK;
         const hipStream_t s = static_cast<hipStream_t>(stream);
-        // the accumulators live for this call only: it returns once the outputs are written
-        DevBuf acc;
-        const uint64_t cells = n_owners * num_docs;
-        if (int rc = acc.ensure(cells * 16)) return rc;
-        auto* sum = acc.as<unsigned long long>();
-        auto* key = sum + cells;
-        HIPCHK(hipMemsetAsync(sum, 0, cells * 8, s));
-        HIPCHK(hipMemsetAsync(key, 0xFF, cells * 8, s));
-        HIPCHK(launch_mlst_chunk_acc(d_hits, n_chunks, num_docs, d_owner_begin, 1, n_owners, threshold, 0, sum, key, s));
-        HIPCHK(launch_mlst_owner_top(sum, key, n_owners, num_docs, nullptr, 0, d_top, d_top_score, d_n_tied, out_stride,
-                                     s));
+        OwnerAcc acc;
+        if (int rc = acc.fill(d_hits, n_chunks, num_docs, d_owner_begin, n_owners, threshold, s)) return rc;
+        HIPCHK(launch_mlst_owner_top(acc.sum, acc.key, n_owners, num_docs, nullptr, 0, d_top, d_top_score, d_n_tied,
+                                     out_stride, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return XS_OK;
+    });
+}
+
+int xs_mlst_ranks_device(const uint32_t* d_hits, uint64_t n, uint64_t num_docs, uint32_t n_ranks, uint32_t* d_top,
+                         uint32_t* d_top_score, uint32_t* d_n_tied, uint64_t top_stride, uint32_t* d_rank_allele,
+                         uint32_t* d_rank_score, uint64_t rank_stride, void* stream) {
+    return xs::guard([&]() -> int {
+        if ((!d_hits || !d_rank_allele || !d_rank_score) && n) return fail(XS_ERR_ARG, "null argument");
+        if (num_docs == 0 || num_docs > 0xFFFFFFFFull) return fail(XS_ERR_ARG, "num_docs must be in 1 .. 2^32-1");
+        if (n_ranks == 0 || n_ranks > kMlstMaxRanks) return fail(XS_ERR_ARG, "n_ranks must be in 1 .. %u", kMlstMaxRanks);
+        if (rank_stride < n_ranks) return fail(XS_ERR_ARG, "rank_stride must be >= n_ranks");
+        if ((d_top || d_top_score || d_n_tied) && top_stride == 0) return fail(XS_ERR_ARG, "top_stride must be >= 1");
+        HIPCHK(launch_mlst_ranks(d_hits, n, num_docs, n_ranks, d_top, d_top_score, d_n_tied, top_stride, d_rank_allele,
+                                 d_rank_score, rank_stride, static_cast<hipStream_t>(stream)));
+        return XS_OK;
+    });
+}
+
+int xs_mlst_chunk_ranks_device(const uint32_t* d_hits, uint64_t n_chunks, uint64_t num_docs,
+                               const uint64_t* d_owner_begin, uint64_t n_owners, uint32_t threshold, uint32_t n_ranks,
+                               uint32_t* d_rank_allele, uint32_t* d_rank_score, uint64_t rank_stride, void* stream) {
+    return xs::guard([&]() -> int {
+        if ((n_owners && (!d_owner_begin || !d_rank_allele || !d_rank_score)) || (n_chunks && !d_hits))
+            return fail(XS_ERR_ARG, "null argument");
+        if (num_docs == 0 || num_docs > 0xFFFFFFFFull) return fail(XS_ERR_ARG, "num_docs must be in 1 .. 2^32-1");
+        if (n_ranks == 0 || n_ranks > kMlstMaxRanks) return fail(XS_ERR_ARG, "n_ranks must be in 1 .. %u", kMlstMaxRanks);
+        if (rank_stride < n_ranks) return fail(XS_ERR_ARG, "rank_stride must be >= n_ranks");
+        if (n_chunks >= (1ull << 32)) return fail(XS_ERR_ARG, "at most 2^32-1 chunks per call");
+        if (n_owners == 0) return XS_OK;
+        const hipStream_t s = static_cast<hipStream_t>(stream);
+        OwnerAcc acc;
+        if (int rc = acc.fill(d_hits, n_chunks, num_docs, d_owner_begin, n_owners, threshold, s)) return rc;
+        HIPCHK(launch_mlst_owner_ranks(acc.sum, acc.key, n_owners, num_docs, nullptr, 0, n_ranks, d_rank_allele,
+                                       d_rank_score, rank_stride, s));
         HIPCHK(hipStreamSynchronize(s));
         return XS_OK;
     });

@@ -11,7 +11,8 @@ record of a locus (and every short record) is probed in one batched GPU call
 (xs_mlst_query) instead of one COBS call per chunk, and the > 50 chunk sums
 are made on the device.  ``predict_columnar`` types many records without the
 per-record dictionaries: all loci in one call (xs_mlst_type_contigs), each hit
-row, and each contig's chunk sums, reduced on the device to the top allele.  The PubMLST strain-type POST (``:295-302``) is network I/O and is
+row, and each contig's chunk sums, reduced on the device to the top allele (with
+``limit=True`` also to the ``limit_number`` best alleles, xs_mlst_type_ranked).  The PubMLST strain-type POST (``:295-302``) is network I/O and is
 delegated to ``strain_type_resolver``.
 """
 from __future__ import annotations
@@ -22,8 +23,8 @@ from pathlib import Path
 
 import numpy as np
 
-from ._lib import XS_BANK_COBS_COMPACT
-from .bank import Bank, cobs_signature_size, mlst_type_contigs
+from ._lib import XS_BANK_COBS_COMPACT, XS_MLST_MAX_RANKS
+from .bank import Bank, cobs_signature_size, mlst_type_contigs, mlst_type_ranked
 from .file_io import (check_input_path, file_reader_device, get_record_iterator, is_record, read_batches,
                       seq_text)
 from .packing import PackedIds, pack_sequences
@@ -295,18 +296,23 @@ class ProbabilisticFilterMlstSchemeModel(ProbabilisticFilterModel):
         return MlstResult(self.model_display_name, step, hits, None)
 
     # ------------------------------------------------------------ columnar typing
-    def _type_batch(self, reads, lengths: np.ndarray, step: int):
+    def _type_batch(self, reads, lengths: np.ndarray, step: int, ranks: int = 0):
         """One batch typed in one xs_mlst_type_contigs call over all loci: records
         shorter than 10 kbp by their hit row's top allele, longer ones cut into
         chunks, scored and reduced on the device (no chunk left above the
         threshold at a locus: XS_MLST_NONE, 0, 0).  Nothing of the batch returns
-        to the host but the three columns."""
+        to the host but the three columns, and with ``ranks`` the N best alleles
+        per record and locus and their scores (xs_mlst_type_ranked)."""
         if (lengths <= self.k).any():
             raise ValueError("Invalid sequence, must be longer than k")
+        if ranks:
+            top, score, tied, _, ra, rs = mlst_type_ranked(self.indices, reads, self.avg_locus_bp_size, ranks, step)
+            return top, score.astype(np.uint64), tied, ra, rs.astype(np.uint64)
         top, score, tied, _ = mlst_type_contigs(self.indices, reads, self.avg_locus_bp_size, step)
         return top, score.astype(np.uint64), tied
 
-    def predict_columnar(self, sequence_input, step: int = 1) -> MlstColumnarResult:
+    def predict_columnar(self, sequence_input, step: int = 1, limit: bool = False,
+                         limit_number: int = 5) -> MlstColumnarResult:
         """The typing as a MlstColumnarResult: per record and locus the top
         allele, its score and how many alleles share it, and per record the
         sufficiency flag, the numbers ``predict`` puts under "Strain type"
@@ -315,9 +321,15 @@ class ProbabilisticFilterMlstSchemeModel(ProbabilisticFilterModel):
         alike, goes through one xs_mlst_type_contigs call over all loci (reads
         uploaded once; rows, chunks and chunk sums reduced on the device); a path
         is read batch by batch, by the device reader where the species model's
-        file path would use it."""
+        file path would use it.  ``limit=True`` also keeps the ``limit_number``
+        (1 .. 8) best alleles per record and locus, reduced on the device in the
+        same call (xs_mlst_type_ranked): the result then gives ``predict(limit=True)``'s
+        "All results" (``all_results``, ``to_mlst_result``)."""
         if step < 1:
             raise ValueError("step must be >= 1")
+        if limit and not 1 <= limit_number <= XS_MLST_MAX_RANKS:
+            raise ValueError(f"limit_number must be in 1 .. {XS_MLST_MAX_RANKS} (XS_MLST_MAX_RANKS)")
+        ranks = int(limit_number) if limit else 0
         if isinstance(sequence_input, Path):
             check_input_path(sequence_input)
             if not self.indices:  # predict reads every record (and checks its length) before it says so
@@ -328,7 +340,7 @@ class ProbabilisticFilterMlstSchemeModel(ProbabilisticFilterModel):
             dev = file_reader_device(self.indices[0])
             ids, parts = [], []
             for batch in read_batches(sequence_input, device=dev):
-                parts.append(self._type_batch(batch if dev is not None else batch.packed, batch.lengths(), step))
+                parts.append(self._type_batch(batch if dev is not None else batch.packed, batch.lengths(), step, ranks))
                 ids.append(batch.ids_packed())
             ids = PackedIds.concat(ids) if ids else []
         else:
@@ -353,13 +365,17 @@ class ProbabilisticFilterMlstSchemeModel(ProbabilisticFilterModel):
             if not self.indices:
                 raise ValueError("The model has not been trained yet")
             ids = [r.id for r in records]
-            parts = [self._type_batch(pack_sequences(texts), lengths, step)] if texts else []
+            parts = [self._type_batch(pack_sequences(texts), lengths, step, ranks)] if texts else []
         L = len(self.indices)
-        cols = [np.concatenate([p[c] for p in parts]) if parts else np.zeros((0, L), dt)
-                for c, dt in enumerate((np.uint32, np.uint64, np.uint32))]
+        shapes = [((0, L), np.uint32), ((0, L), np.uint64), ((0, L), np.uint32)]
+        if ranks:
+            shapes += [((0, L, ranks), np.uint32), ((0, L, ranks), np.uint64)]
+        cols = [np.concatenate([p[c] for p in parts]) if parts else np.zeros(shape, dt)
+                for c, (shape, dt) in enumerate(shapes)]
+        rank_cols = {"rank_allele": cols[3], "rank_score": cols[4]} if ranks else {}
         return MlstColumnarResult(self.model_display_name, step, ids, list(self.loci.keys()),
                                   [bank.doc_names for bank in self.indices], list(self.avg_locus_bp_size),
-                                  cols[0], cols[1], cols[2], None)
+                                  cols[0], cols[1], cols[2], None, **rank_cols)
 
     def close(self) -> None:
         for bank in self.indices:

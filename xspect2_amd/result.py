@@ -359,12 +359,28 @@ class MlstColumnarResult:
     order); ``XS_MLST_NONE`` is the reference's "N/A" (a record of 10 kbp or
     more none of whose chunks passed at that locus), with score 0 and
     ``n_tied`` 0.  ``n_tied`` is not in the reference: 1 means the call is
-    unique at that locus.  ``ids`` may be a ``PackedIds``."""
+    unique at that locus.  ``ids`` may be a ``PackedIds``.
+
+    ``rank_allele`` / ``rank_score`` (both or neither, [n, L, N]) are the N best
+    alleles per record and locus in the reference's order, its ``limit`` /
+    ``limit_number`` (:258-259, 278-282); rank 0 is the top allele, and ranks a
+    locus does not fill hold ``XS_MLST_NONE``, 0.  With them ``all_results``,
+    ``to_mlst_result`` and two more ``to_dict`` keys are available."""
 
     def __init__(self, scheme_model: str, steps: int, ids, loci: list[str], allele_names: list[list[str]],
                  locus_size: list[int], top_allele: np.ndarray, top_score: np.ndarray, n_tied: np.ndarray,
-                 input_source: str | None = None):
+                 input_source: str | None = None, *, rank_allele: np.ndarray | None = None,
+                 rank_score: np.ndarray | None = None):
         n, L = len(ids), len(loci)
+        if (rank_allele is None) != (rank_score is None):
+            raise ValueError("rank_allele and rank_score come together")
+        self.rank_allele = self.rank_score = None
+        if rank_allele is not None:
+            self.rank_allele = np.ascontiguousarray(rank_allele, dtype=np.uint32)
+            self.rank_score = np.ascontiguousarray(rank_score, dtype=np.uint64)
+            shape = self.rank_allele.shape
+            if self.rank_allele.ndim != 3 or shape[:2] != (n, L) or shape[2] < 1 or self.rank_score.shape != shape:
+                raise ValueError("rank_allele and rank_score must be [len(ids), len(loci), n_ranks], n_ranks >= 1")
         self.top_allele = np.ascontiguousarray(top_allele, dtype=np.uint32).reshape(-1, L)
         self.top_score = np.ascontiguousarray(top_score, dtype=np.uint64).reshape(-1, L)
         self.n_tied = np.ascontiguousarray(n_tied, dtype=np.uint32).reshape(-1, L)
@@ -445,16 +461,47 @@ class MlstColumnarResult:
         """``{id: strain_type(i)}``: per-record dictionaries, for small inputs."""
         return {rid: self.strain_type(i, resolver, scheme_url) for i, rid in enumerate(self.ids)}
 
+    def _ranked(self) -> None:
+        if self.rank_allele is None:
+            raise ValueError("this result carries no ranks (predict_columnar(..., limit=True))")
+
+    def all_results(self, i: int) -> dict:
+        """The dict ``predict(limit=True)`` puts under ``hits[id][1]["All results"]``
+        for record i: ``{locus: {allele: score, ...}}``, the alleles in rank
+        order.  A locus without an allele (``XS_MLST_NONE`` at rank 0: a record
+        of 10 kbp or more none of whose chunks passed there) is left out;
+        ``predict()`` gives its "could not be detected" string in place of the
+        dict there, or raises when a later locus has alleles."""
+        self._ranked()
+        res: dict = {}
+        for l, locus in enumerate(self.loci):
+            names = self.allele_names[l]
+            row = {names[a]: s for a, s in zip(self.rank_allele[i, l].tolist(), self.rank_score[i, l].tolist())
+                   if a != XS_MLST_NONE}
+            if row:
+                res[locus] = row
+        return res
+
+    def to_mlst_result(self, resolver=None, scheme_url: str | None = None) -> MlstResult:
+        """The ``MlstResult`` of ``predict(limit=True)``: per record
+        ``[{"Strain type": strain_type(i)}, {"All results": all_results(i)}]``."""
+        self._ranked()
+        hits = {rid: [{"Strain type": self.strain_type(i, resolver, scheme_url)}, {"All results": self.all_results(i)}]
+                for i, rid in enumerate(self.ids)}
+        return MlstResult(self.scheme_model, self.steps, hits, self.input_source)
+
     def to_dict(self) -> dict:
         """The columnar JSON layout: one list per locus and column,
-        aligned with "ids"; allele names spelled out, "N/A" where there is none."""
+        aligned with "ids"; allele names spelled out, "N/A" where there is none.
+        With ranks: "ranked_alleles" / "ranked_scores", per locus one list of
+        n_ranks entries per record."""
         miss = self._missing()
 
         def names(l: int) -> list[str]:
             tbl = self.allele_names[l]
             return ["N/A" if m else tbl[a] for a, m in zip(self.top_allele[:, l].tolist(), miss[:, l].tolist())]
 
-        return {
+        out = {
             "Scheme": self.scheme_model,
             "Steps": self.steps,
             "Input_source": self.input_source,
@@ -466,6 +513,14 @@ class MlstColumnarResult:
             "n_tied": {locus: self.n_tied[:, l].tolist() for l, locus in enumerate(self.loci)},
             "sufficient": self.sufficient.tolist(),
         }
+        if self.rank_allele is not None:
+            def ranked(l: int) -> list[list[str]]:
+                tbl = self.allele_names[l]
+                return [["N/A" if a == XS_MLST_NONE else tbl[a] for a in row] for row in self.rank_allele[:, l].tolist()]
+
+            out["ranked_alleles"] = {locus: ranked(l) for l, locus in enumerate(self.loci)}
+            out["ranked_scores"] = {locus: self.rank_score[:, l].tolist() for l, locus in enumerate(self.loci)}
+        return out
 
     def save(self, path: Path | str) -> None:
         path = Path(path)
