@@ -143,7 +143,13 @@ const char* xs_bank_doc_name(const xs_bank* bank, uint64_t i);
 /* Probe n reads (host buffers): read r = seqs[offsets[r] .. offsets[r+1]).
  * hits_out: n x D uint32 (row-major, may be NULL), num_kmers_out: n (may be
  * NULL).  k-mers are taken at positions i*step, i < ceil((len-k+1)/step);
- * reads shorter than k contribute no k-mers. */
+ * reads shorter than k contribute no k-mers.
+ * Outputs, here and in xs_query_hits, xs_query_totals and xs_query_best: the
+ * caller initialises none of them.  A successful call writes every element of
+ * every output it is given (n x D hits, n k-mer counts, n best docs and best
+ * hits, D or D+1 totals; a read without k-mers gets a row of zeros) and no
+ * byte outside them; a call refused because a count may not fit hit_bytes
+ * writes nothing.  n = 0 writes the totals only (zeros). */
 int xs_query(xs_bank* bank, const char* seqs, const uint64_t* offsets, uint64_t n, uint32_t step,
              uint32_t* hits_out, uint64_t* num_kmers_out);
 
@@ -187,7 +193,12 @@ int xs_query_totals(xs_bank* bank, const char* seqs, const uint64_t* offsets, ui
  * ordered with all blocking streams; pass torch.cuda.current_stream().cuda_stream).
  * d_seqs holds seq_bytes bytes; d_offsets n+1 uint64.  Any of d_hits (n x D
  * uint32), d_num_kmers (n uint64) and d_totals (D+1 uint64: per-doc totals then
- * the k-mer total) may be NULL.  The bank must live on the current device. */
+ * the k-mer total) may be NULL.  The bank must live on the current device.
+ * No output needs initialising by the caller (the library zeroes the rows it
+ * accumulates into, the buffers may hold anything), and nothing outside n x D
+ * hits, n k-mer counts and D+1 totals is written; the outputs need 4-byte
+ * (hits) and 8-byte alignment only.  n = 0 zeroes d_totals and writes nothing
+ * else. */
 int xs_query_device(xs_bank* bank, const void* d_seqs, uint64_t seq_bytes,
                     const uint64_t* d_offsets, uint64_t n, uint32_t step, uint32_t* d_hits,
                     uint64_t* d_num_kmers, uint64_t* d_totals, void* stream);

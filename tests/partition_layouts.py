@@ -1,7 +1,8 @@
 """Read layouts that put read boundaries on the partitioned probes' edges.
 
-Helper of tests/test_partition_layouts.py (CPU) and
-tests/test_gpu_partitioned_edges.py (GPU); it needs no GPU and no library.
+Helper of tests/test_partition_layouts.py and tests/test_output_buffer_checker.py
+(CPU), tests/test_gpu_partitioned_edges.py and tests/test_gpu_output_buffers.py
+(GPU); it needs no GPU and no library.
 
 The partitioned probes (xs_probe_cobspart.hip, xs_probe_bloompart.hip) give
 every sampled k-mer of a call a global id and work on bucket blocks of T
@@ -311,3 +312,128 @@ def double_added_rows(counts, T: int) -> list[int]:
     """What a probe would count that stored an "added" read's row and then added
     to it as well (or never zeroed it after an equal earlier call)."""
     return [2 * c if cls == "added" else c for c, cls in zip(counts, read_classes(counts, T))]
+
+
+# ---------------------------------------------------------------- output buffers
+# No probe path clears the hit matrix: a row is stored whole by the kernel that
+# owns every k-mer of its read, and otherwise zeroed by separate code and built
+# up with atomicAdd (skipped when the count is 0).  Whether the two agree shows
+# only when the output does not happen to hold zeros already, so the tests of
+# tests/test_gpu_output_buffers.py hand over outputs laid out as
+# [head guard | body | tail guard] in one allocation, every byte a poison.
+GUARD_ELEMS = 64            # elements of the output's type in each guard, at the least
+POISON_BYTES = (0xFF, 0x5A)  # every byte: 0xFFFFFFFF (a count c added onto it wraps to c - 1) and 0x5A5A5A5A (+ c)
+
+
+def unit_classes(counts) -> list[str]:
+    """What the direct probes do with every read's hit row: "empty" (no work
+    unit: zeroed, never visited), "whole" (one unit of up to kSegKmers k-mers:
+    stored, never zeroed) or "split" (two units or more: zeroed, then added
+    atomically by each).  The direct-path counterpart of read_classes."""
+    out = []
+    for c in counts:
+        s = -(-int(c) // SEG_KMERS)
+        out.append("empty" if s == 0 else "whole" if s == 1 else "split")
+    return out
+
+
+def poison_of(byte: int, dtype) -> int:
+    """The value an untouched element of `dtype` reads as."""
+    return int.from_bytes(bytes([byte]) * np.dtype(dtype).itemsize, "little")
+
+
+def guarded_bytes(count: int, dtype) -> int:
+    """Bytes of one allocation that holds `count` elements between two guards at any phase."""
+    return (count + 2 * GUARD_ELEMS) * np.dtype(dtype).itemsize + 16
+
+
+def body_offset(addr: int, dtype, phase: int) -> int:
+    """Byte offset of the body in an allocation at `addr`: the first one past a
+    whole head guard at which the body's address is `phase` (mod 16)."""
+    size = np.dtype(dtype).itemsize
+    assert phase % size == 0 and 0 <= phase < 16
+    off = GUARD_ELEMS * size
+    return off + (phase - (addr + off)) % 16
+
+
+def check_guards(raw: np.ndarray, off: int, nbytes: int, byte: int, what: str = "") -> None:
+    """Both guards of a guarded allocation (all of it, as bytes) still hold the poison."""
+    assert raw.dtype == np.uint8 and raw.ndim == 1 and off + nbytes <= raw.size
+    head = np.flatnonzero(raw[:off] != byte)
+    tail = np.flatnonzero(raw[off + nbytes:] != byte)
+    assert head.size == 0, (f"{what}: {head.size} byte(s) written before the output, the nearest "
+                            f"{off - int(head[-1])} byte(s) before its first element")
+    assert tail.size == 0, (f"{what}: {tail.size} byte(s) written past the output, the nearest "
+                            f"{int(tail[0])} byte(s) after its last element")
+
+
+class GuardedArray:
+    """A host output of `count` elements of `dtype` between two guards, every
+    byte of the allocation `byte`; `body` is what the library is handed, at an
+    address of `phase` (mod 16).  alloc(nbytes) -> uint8 array of 16-byte
+    aligned memory (numpy's own by default; pinned memory for one case)."""
+
+    def __init__(self, count: int, dtype, byte: int, phase: int = 0, alloc=None):
+        self.dtype, self.byte = np.dtype(dtype), byte
+        total = guarded_bytes(count, dtype)
+        self.raw = alloc(total) if alloc is not None else np.empty(total, dtype=np.uint8)
+        assert self.raw.dtype == np.uint8 and self.raw.size == total
+        self.raw[:] = byte
+        self.off = body_offset(self.raw.ctypes.data, dtype, phase)
+        self.nbytes = count * self.dtype.itemsize
+        self.body = self.raw[self.off:self.off + self.nbytes].view(self.dtype)
+        assert self.body.ctypes.data % 16 == phase and self.off + self.nbytes + GUARD_ELEMS * self.dtype.itemsize <= total
+
+    @property
+    def ptr(self) -> int:
+        return self.body.ctypes.data
+
+    def check(self, what: str = "") -> np.ndarray:
+        check_guards(self.raw, self.off, self.nbytes, self.byte, what)
+        return self.body.copy()
+
+
+def explain_rows(got, want, classes, byte: int | None) -> str | None:
+    """None when the matrices are equal; else the first wrong row, its read
+    class, and what its first wrong cell looks like against the poison (byte
+    None: the output was not poisoned, it held an earlier answer)."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, f"shape {got.shape} against {want.shape}"
+    g2, w2 = got.reshape(len(classes), -1), want.reshape(len(classes), -1)
+    bad = np.flatnonzero((g2 != w2).any(axis=1))
+    if bad.size == 0:
+        return None
+    r = int(bad[0])
+    d = int(np.flatnonzero(g2[r] != w2[r])[0])
+    g, w = int(g2[r, d]), int(w2[r, d])
+    looks = "a wrong value"
+    if byte is not None:
+        p = poison_of(byte, got.dtype)
+        mask = (1 << (8 * got.dtype.itemsize)) - 1
+        looks = ("never written" if g == p else "added onto what the buffer held" if g == (p + w) & mask and w
+                 else looks)
+    return (f"{bad.size} of {len(classes)} rows differ, first row {r} ({classes[r]}): cell {d} is {g:#x}, "
+            f"want {w:#x}: {looks}; classes of the wrong rows {sorted({classes[int(i)] for i in bad})}")
+
+
+def assert_rows(got, want, classes, byte: int | None, what: str = "") -> None:
+    msg = explain_rows(got, want, classes, byte)
+    assert msg is None, f"{what}: {msg}"
+
+
+def write_rows(body: np.ndarray, want: np.ndarray, untouched=(), added=(), sparse=()) -> None:
+    """Model of a library writing the matrix `want` into the output `body`
+    (same shape): rows `untouched` are never written, rows `added` are added
+    onto what the buffer held (not zeroed first), rows `sparse` are stored
+    without their zero cells; every other row is stored whole."""
+    assert body.shape == want.shape
+    for r in range(want.shape[0]):
+        if r in untouched:
+            continue
+        if r in added:
+            body[r] += want[r].astype(body.dtype)  # wraps, as the device's unsigned add does
+        elif r in sparse:
+            nz = want[r] != 0
+            body[r][nz] = want[r][nz]
+        else:
+            body[r] = want[r]

@@ -715,9 +715,10 @@ def test_device_api_with_torch_stream(xs, oracle_mod):
     dev = torch.device("cuda", 0)
     d_seqs = torch.from_numpy(buf.copy()).to(dev)
     d_offs = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    d_hits = torch.empty((len(reads), 100), dtype=torch.int32, device=dev)
-    d_nk = torch.empty(len(reads), dtype=torch.int64, device=dev)
-    d_tot = torch.empty(101, dtype=torch.int64, device=dev)
+    # outputs full of a poison: the library initialises every cell itself
+    d_hits = torch.full((len(reads), 100), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    d_nk = torch.full((len(reads),), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device=dev)
+    d_tot = torch.full((101,), -1, dtype=torch.int64, device=dev)
     s = torch.cuda.current_stream()
     gb.query_device(d_seqs, buf.size, d_offs, len(reads), 1, d_hits, d_nk, d_tot, stream=s.cuda_stream)
     torch.cuda.synchronize()
@@ -768,8 +769,8 @@ def test_device_queries_on_mixed_streams(xs, oracle_mod, kind):
         pr = pack_sequences(reads)
         d_seq = torch.from_numpy(pr.buf[:max(1, int(pr.offsets[-1]))].copy()).to(dev)
         d_off = torch.from_numpy(pr.offsets.astype(np.int64)).to(dev)
-        d_hits = torch.empty((pr.n, cols), dtype=torch.int32, device=dev)
-        d_nk = torch.empty(pr.n, dtype=torch.int64, device=dev)
+        d_hits = torch.full((pr.n, cols), -1 if i % 2 else 0x5A5A5A5A, dtype=torch.int32, device=dev)  # poisoned
+        d_nk = torch.full((pr.n,), -1 if i % 2 else 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device=dev)
         jobs.append((reads, pr, d_seq, d_off, d_hits, d_nk))
     torch.cuda.synchronize()
     host = []
@@ -822,8 +823,8 @@ def test_device_api_unaligned_tight_buffers(xs, oracle_mod, shift):
         assert d_seqs.data_ptr() % 4 == shift % 4 and d_seqs.numel() == lead + len(body)
         d_offs = torch.from_numpy(offs.astype(np.int64)).to(dev)
         cols = 1 if bloom else D
-        d_hits = torch.empty((len(reads), cols), dtype=torch.int32, device=dev)
-        d_nk = torch.empty(len(reads), dtype=torch.int64, device=dev)
+        d_hits = torch.full((len(reads), cols), -1 if shift % 2 else 0x5A5A5A5A, dtype=torch.int32, device=dev)  # poisoned
+        d_nk = torch.full((len(reads),), -1 if shift % 2 else 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device=dev)
         gb.query_device(d_seqs, d_seqs.numel(), d_offs, len(reads), 1, d_hits, d_nk, None,
                         stream=torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
