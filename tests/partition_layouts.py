@@ -1,8 +1,9 @@
 """Read layouts that put read boundaries on the partitioned probes' edges.
 
-Helper of tests/test_partition_layouts.py and tests/test_output_buffer_checker.py
-(CPU), tests/test_gpu_partitioned_edges.py and tests/test_gpu_output_buffers.py
-(GPU); it needs no GPU and no library.
+Helper of tests/test_partition_layouts.py, tests/test_output_buffer_checker.py
+and tests/test_large_extents_host.py (CPU), tests/test_gpu_partitioned_edges.py,
+tests/test_gpu_output_buffers.py and tests/test_gpu_large_extents.py (GPU); it
+needs no GPU and no library.
 
 The partitioned probes (xs_probe_cobspart.hip, xs_probe_bloompart.hip) give
 every sampled k-mer of a call a global id and work on bucket blocks of T
@@ -246,27 +247,36 @@ def make_reads(rng, counts, k: int, step: int) -> list[bytes]:
 
 
 # ---------------------------------------------------------------- plans
-def cobs_plan(sig: int, h: int, mode: int, kbound: int = 0, workspace_mib: int | None = None) -> dict:
-    """cobs_part_plan restated for modes 3 and 4: partition shift and count,
-    run padding, entries per block, and blocks per workspace range."""
-    assert mode in (3, 4)
-
+def part_shift(size: int, pref: int, floor: int) -> int:
+    """part_shift of xs_part.h: 2^pref units per partition, halved down to 2^floor
+    while that leaves fewer than 64 partitions, doubled while more than kPartMax."""
     def parts(s):
-        return (sig + (1 << s) - 1) >> s
+        return (size + (1 << s) - 1) >> s
 
-    shift = 10 if mode == 4 else 17
-    while mode != 4 and shift > 10 and parts(shift) < 64:
+    shift = pref
+    while shift > floor and parts(shift) < 64:
         shift -= 1
     while parts(shift) > PART_MAX:
         shift += 1
-    P = parts(shift)
+    return shift
+
+
+def cobs_plan(sig: int, h: int, mode: int, kbound: int = 0, workspace_mib: int | None = None) -> dict:
+    """cobs_part_plan restated: partition shift and count, run padding, entries
+    per block, and blocks per workspace range.  Modes 1 and 2 (production:
+    2^17-row partitions down to 2^13), 3 (down to 2^10) and 4 (2^10 rows);
+    any signature size the planner takes (below 2^30 rows)."""
+    assert mode in (1, 2, 3, 4) and 0 < sig < 1 << 30
+    shift = part_shift(sig, 10, 10) if mode == 4 else part_shift(sig, 17, 10 if mode == 3 else 13)
+    assert shift + ID_BITS < 32, "the planner declines: a row and a k-mer id no longer fit one entry"
+    P = (sig + (1 << shift) - 1) >> shift
     pad = 4 if P <= COBS_PAD_PARTS else 1
     stride = (COBS_CK * h + (pad - 1) * P + 7) // 8 * 8
     plan = {"shift": shift, "P": P, "pad": pad, "stride": stride, "last_rows": sig - ((P - 1) << shift)}
     if workspace_mib is not None:
         nblk = -(-kbound // COBS_CK)
         plan["nblk"] = nblk
-        plan["rblk"] = max(1, min(nblk, (max(1, workspace_mib) << 20) // (stride * 20)))
+        plan["rblk"] = max(1, min(nblk, (max(1, workspace_mib) << 20) // (stride * 20), ((1 << 32) - 1) // stride))
         plan["ranges"] = -(-nblk // plan["rblk"])
     return plan
 
@@ -276,12 +286,13 @@ def kbound(reads, step: int) -> int:
     return sum(len(r) for r in reads) // step + len(reads) + 1
 
 
-def bloom_plan(nbytes: int) -> dict:
-    """bloom_part_plan restated for mode 3: partitions of 1024 bits, doubled while over kPartMax."""
+def bloom_plan(nbytes: int, mode: int = 3) -> dict:
+    """bloom_part_plan restated: mode 3, partitions of 1024 bits, doubled while
+    over kPartMax; modes 1 and 2 (production), 2^24-bit partitions down to 2^20
+    while fewer than 64, doubled while over kPartMax."""
+    assert mode in (1, 2, 3)
     mbits = nbytes * 8
-    shift = 10
-    while (mbits + (1 << shift) - 1) >> shift > PART_MAX:
-        shift += 1
+    shift = part_shift(mbits, 10, 10) if mode == 3 else part_shift(mbits, 24, 20)
     P = (mbits + (1 << shift) - 1) >> shift
     return {"shift": shift, "P": P, "last_bits": mbits - ((P - 1) << shift)}
 

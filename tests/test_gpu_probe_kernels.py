@@ -91,13 +91,15 @@ def _rows():
 
 ROWS = _rows()
 
-# Compiled, but only reached by a bank with a group of >= 2^28 rows (the fast
-# kernel's limit) or >= 2^30 rows (fastmod_small's limit in wide and vslice):
-# every smaller bank of their shape is taken by fast, vslice or wide first.
-# No bank XspecT trains is that large; DESIGN.md lists them.
+# Compiled, but only reached by a bank with a group of >= 2^30 rows
+# (fastmod_small's limit in wide and vslice; 137 GB at 128 bytes a row): every
+# smaller bank of their shape is taken by vslice or wide first.  No bank XspecT
+# trains is that large; DESIGN.md lists them.  slots<21,7,1,4> and
+# slots<31,1,1,4>, which take the classic banks of <= 128 docs over the fast
+# kernel's limit of 2^28 rows, have their case in
+# tests/test_gpu_large_extents.py (B4: 300,000,007 rows, a 4.8 GB image).
+LARGE_EXTENT_CASES = {"slots<21,7,1,4>", "slots<31,1,1,4>"}
 UNREACHABLE_AT_TEST_SIZE = {
-    "slots<21,7,1,4>": "classic <= 128 docs, (21, 7): fast takes it below 2^28 rows",
-    "slots<31,1,1,4>": "classic <= 128 docs, (31, 1): fast takes it below 2^28 rows",
     "slots<21,7,1,8>": "classic 513-1024 docs: wide<C8> takes it below 2^30 rows",
     "slots<31,1,1,8>": "classic 513-1024 docs: wide<C8> takes it below 2^30 rows",
     "slots<0,0,1,8>": "classic 513-1024 docs: wide<C8> takes it below 2^30 rows",
@@ -287,12 +289,17 @@ def test_vslice_takes_512_doc_slices_of_a_classic_bank(xs, oracle_mod, tmp_path)
 
 
 def test_every_compiled_kernel_has_a_case(xs):
-    """The table's kernels plus the 13 no bank of test size reaches are exactly
-    the instantiations the library compiled: a new instantiation needs a case,
-    a case whose kernel is gone fails."""
+    """The table's kernels, the two with a case among the large banks of
+    tests/test_gpu_large_extents.py, plus the 11 no bank of test size reaches
+    are exactly the instantiations the library compiled: a new instantiation
+    needs a case, a case whose kernel is gone fails."""
+    import test_gpu_large_extents as large
     compiled = xs.probe_kernel_names()
     assert len(compiled) == len(set(compiled)) == 57
     covered = {r[5] for r in ROWS}
-    assert len(covered) == 44 and len(UNREACHABLE_AT_TEST_SIZE) == 13
+    large_routes = {route[1] for case in large.COBS_CASES for route in case.values[-1]}
+    assert LARGE_EXTENT_CASES <= large_routes and not covered & LARGE_EXTENT_CASES
+    covered |= LARGE_EXTENT_CASES
+    assert len(covered) == 46 and len(UNREACHABLE_AT_TEST_SIZE) == 11
     assert not covered & set(UNREACHABLE_AT_TEST_SIZE)
     assert covered | set(UNREACHABLE_AT_TEST_SIZE) == set(compiled)
