@@ -103,10 +103,40 @@ int xs_bank_open(const char* path, int kind, int device, xs_bank** out);
  * the per-read hit columns are then all-gathered (xspect2_amd.distributed). */
 int xs_bank_open_docs(const char* path, int device, uint64_t doc_lo, uint64_t doc_hi, xs_bank** out);
 
+/* A bank file's header, read and checked with no device work (no reference
+ * counterpart: cobs_index.Search and rbloom.load read the whole file).  *out as
+ * xs_bank_info fills it after an open, with device = -1; device_bytes and
+ * device_row_pitch are what an open of the whole file allocates, so a caller
+ * knows the HBM a model needs before it opens it.  *payload_offset (may be
+ * NULL): the file offset of the payload's first byte.
+ * Every file refused here is refused by xs_bank_open and xs_bank_open_docs with
+ * the same code, before their first HIP call and with *out left NULL;
+ * xs_last_error names the path.  XS_ERR_FORMAT: a wrong magic or trailer,
+ * version != 1, a header the file's end cuts off, more doc names (or compact
+ * groups) than bytes left, per-group num_hashes that differ, zero docs, zero
+ * signature or page size, groups that do not cover the docs, a size that does
+ * not fit 64 bits (sum(signature sizes) * page size, the compact padding), or
+ * a payload that is not exactly the bytes the header implies.
+ * XS_ERR_UNSUPPORTED: term_size outside 1..32, num_hashes / rbloom K (compared
+ * at their full 64 bits) outside 1..16, canonicalize != 1.
+ * One limit is the handle's, not the file's, and is not applied here: the
+ * probe's LDS counters hold at most 8192 docs.  xs_bank_open refuses a file of
+ * more docs (XS_ERR_UNSUPPORTED, also before any HIP call); xs_bank_open_docs
+ * applies the limit to its slice only, so such a bank opens column-split, and
+ * this call reports its doc count for the split.
+ * xs_bank_create_cobs and xs_bank_create_bloom check their arguments the same
+ * way: a size that does not fit 64 bits is XS_ERR_ARG there. */
+int xs_bank_file_info(const char* path, int kind, xs_bank_info_t* out, uint64_t* payload_offset);
+/* The doc names of a bank file that xs_bank_file_info accepts, each followed by
+ * '\n', into buf[cap]; *bytes = the bytes they take.  When *bytes > cap nothing
+ * is written: call again with room for *bytes (buf may be NULL with cap 0). */
+int xs_bank_file_names(const char* path, int kind, char* buf, uint64_t cap, uint64_t* bytes);
+
 /* Create an empty COBS bank (classic: num_groups = 1 and page_size =
  * ceil(num_docs/8); compact: num_groups groups of 8*page_size docs each, the
  * last one partial).  sig[g] = signature size of group g.  doc_names may be
- * NULL (names "0", "1", ...). */
+ * NULL (names "0", "1", ...); a NULL entry is XS_ERR_ARG.  The geometry is
+ * checked before sig's entries and the names are read. */
 int xs_bank_create_cobs(int device, int kind, uint32_t term_size, uint32_t num_hashes,
                         uint64_t num_docs, uint64_t page_size, uint64_t num_groups,
                         const uint64_t* sig, const char* const* doc_names, xs_bank** out);

@@ -392,6 +392,119 @@ def rbloom_file(num_hashes: int, bits: np.ndarray) -> bytes:
     return struct.pack("<Q", num_hashes) + np.ascontiguousarray(bits, dtype=np.uint8).tobytes()
 
 
+class BankFileError(ValueError):
+    """A bank file the layouts above refuse.  kind: "format" (the bytes are not
+    a whole file of the layout) or "unsupported" (a whole file whose k, hash
+    count or canonicalize flag is outside what the device probes)."""
+
+    def __init__(self, kind: str, why: str):
+        super().__init__(f"{kind}: {why}")
+        self.kind = kind
+
+
+def bank_file_geometry(data: bytes, kind: str) -> dict:
+    """The three layouts above read back with Python integers (nothing wraps):
+    kind "classic", "compact" or "rbloom".  Returns k, h, docs, groups, page,
+    sig (list), names (list of bytes) and payload_offset, or raises
+    BankFileError.  A header is read in order and the first thing wrong with it
+    decides; then canonicalize, k in 1..32 and h in 1..16 ("unsupported"); then
+    the geometry and the payload's exact size.  Two refusals are the library's
+    limits restated, not the layout's, so that the classes of refusal can be
+    compared: more than 2^20 compact groups, and more groups than the bytes
+    left hold at 16 bytes each (a cut file either way); the order of the
+    checks follows the library's for the same reason.  Limits of a handle
+    beyond the layout (how many docs a probe block counts) are not this
+    reader's."""
+    pos = 0
+
+    def bad(why):
+        return BankFileError("format", why)
+
+    def take(n):
+        nonlocal pos
+        if pos + n > len(data):
+            raise bad(f"the file ends inside the {n} bytes at {pos}")
+        pos += n
+        return data[pos - n:pos]
+
+    def uint(n):
+        return int.from_bytes(take(n), "little")
+
+    def magic(text):
+        if take(len(text)) != text:
+            raise bad(f"no {text!r} at {pos - len(text)}")
+
+    def names_of(docs):
+        if docs > len(data) - pos:  # a name takes at least its '\n'
+            raise bad(f"{docs} names in {len(data) - pos} bytes")
+        out = []
+        for _ in range(docs):
+            end = data.find(b"\n", pos)
+            if end < 0:
+                raise bad("a name without its newline")
+            out.append(take(end + 1 - pos)[:-1])
+        return out
+
+    if kind == "rbloom":
+        h = uint(8)
+        if len(data) <= 8:
+            raise bad("no filter bytes")
+        k, canon, docs, groups, page, sig, names = 21, 1, 1, 0, 0, [], [b"0"]
+        payload = len(data) - 8
+    elif kind == "classic":
+        magic(b"COBS:")
+        magic(b"CLASSIC_INDEX")
+        version, docs, k, canon, s, h = uint(4), uint(4), uint(4), uint(1), uint(8), uint(8)
+        if version != 1:
+            raise bad(f"version {version}")
+        names = names_of(docs)
+        magic(b"CLASSIC_INDEX")
+        groups, page, sig = 1, (docs + 7) // 8, [s]
+    elif kind == "compact":
+        magic(b"COBS:")
+        magic(b"COMPACT_INDEX")
+        version, k, canon, groups = uint(4), uint(4), uint(1), uint(8)
+        if version != 1:
+            raise bad(f"version {version}")
+        if groups == 0 or groups > 1 << 20 or 16 * groups > len(data) - pos:
+            raise bad(f"{groups} groups")
+        sig, hs = [], []
+        for _ in range(groups):
+            sig.append(uint(8))
+            hs.append(uint(8))
+            if hs[-1] != hs[0]:
+                raise bad("mixed num_hashes")
+        h = hs[0]
+        page, docs = uint(8), uint(4)
+        names = names_of(docs)
+        magic(b"COMPACT_INDEX")
+        if page == 0:
+            raise bad("zero page size")
+        pos += -pos % page
+        if pos > len(data):
+            raise bad("the padding runs past the file's end")
+    else:
+        raise ValueError(f"unknown bank file kind {kind!r}")
+    if canon != 1:
+        raise BankFileError("unsupported", f"canonicalize = {canon}")
+    if not 1 <= k <= 32:
+        raise BankFileError("unsupported", f"term_size {k}")
+    if not 1 <= h <= 16:
+        raise BankFileError("unsupported", f"num_hashes {h}")
+    if kind != "rbloom":
+        if docs == 0:
+            raise bad("no documents")
+        if not (groups - 1) * 8 * page < docs <= groups * 8 * page:
+            raise bad(f"{groups} groups of {8 * page} docs for {docs} docs")
+        if any(s == 0 for s in sig):
+            raise bad("zero signature size")
+        payload = sum(sig) * page  # exact: a product past 2^64 equals no file's size
+    if len(data) - pos != payload:
+        raise bad(f"{len(data) - pos} payload bytes, the header implies {payload}")
+    return {"k": k, "h": h, "docs": docs, "groups": groups, "page": page, "sig": sig, "names": names,
+            "payload_offset": pos}
+
+
 def bloom_indexes_py(hash64: int, nhash: int, mbits: int) -> list[int]:
     """rbloom's K bit indices as restated (UNVERIFIED): a 128-bit LCG
     state <- state * M + C mod 2^128 from state = the XXH3-64 hash, index =

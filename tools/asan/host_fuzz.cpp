@@ -4,7 +4,9 @@
 // size from one byte up, 1..8 parser threads.  Functional equality with
 // Biopython / json.dumps is tested in tests/test_fastx.py and
 // tests/test_json_writer.py; this driver looks for memory errors only.  It also drives the host's plan
-// of a contig typing call (xs_mlst_plan.h) over randomised record lengths and checks its invariants.
+// of a contig typing call (xs_mlst_plan.h) over randomised record lengths and checks its invariants, and the
+// bank file header reader (xs_bank_header.h) over truncations, bit flips, field edges and random splices of
+// five small valid files: every case must end in a return code.
 //   make -C tools/asan run
 #include <atomic>
 #include <cstdarg>
@@ -20,6 +22,7 @@
 #include <vector>
 
 #include "../../include/xspect_hip.h"
+#include "../../xspect2_amd/csrc/xs_bank_header.h"
 #include "../../xspect2_amd/csrc/xs_internal.h"
 #include "../../xspect2_amd/csrc/xs_mlst_plan.h"
 
@@ -221,6 +224,173 @@ static int fuzz_mlst_plan(int* plans) {
     return bad;
 }
 
+// Bank file headers (xs_bank_header.h): five valid files of the three layouts (the shapes of
+// tests/test_bank_file_headers.py), and of each every truncation, every single-bit flip of the header (the
+// fixed fields only where 1430 names make it 5.6 KB), every numeric field at its edge values and 2000 seeded
+// random splices.  Every case ends in XS_OK or an error code; an accepted file's sizes multiply out exactly
+// to the bytes it holds.  Then the argument side of check_geometry over sizes beyond 64 bits.  Returns the
+// broken expectations; *cases counts the files read.
+struct BankFile {
+    int kind;
+    std::string data;
+    std::vector<std::pair<size_t, size_t>> fields;  // offset, width of every numeric field
+    size_t header;                                  // bytes before the payload
+    bool flip_fields_only;
+};
+
+template <class T>
+static void put_le(std::string& s, T v) {
+    s.append(reinterpret_cast<const char*>(&v), sizeof(T));
+}
+
+static BankFile classic_file(uint32_t docs, uint64_t sig) {
+    BankFile f{XS_BANK_COBS_CLASSIC, "COBS:CLASSIC_INDEX", {{18, 4}, {22, 4}, {26, 4}, {30, 1}, {31, 8}, {39, 8}}, 0, false};
+    put_le<uint32_t>(f.data, 1);
+    put_le<uint32_t>(f.data, docs);
+    put_le<uint32_t>(f.data, 21);
+    put_le<uint8_t>(f.data, 1);
+    put_le<uint64_t>(f.data, sig);
+    put_le<uint64_t>(f.data, 7);
+    for (uint32_t i = 0; i < docs; ++i) f.data += "d" + std::to_string(i) + "\n";
+    f.data += "CLASSIC_INDEX";
+    f.header = f.data.size();
+    f.data += rand_seq(sig * ((docs + 7) / 8), "ACGT\n\x01\xff");
+    return f;
+}
+
+static BankFile compact_file(uint32_t docs, std::vector<uint64_t> sig, uint64_t page, bool fields_only) {
+    BankFile f{XS_BANK_COBS_COMPACT, "COBS:COMPACT_INDEX", {{18, 4}, {22, 4}, {26, 1}, {27, 8}}, 0, fields_only};
+    put_le<uint32_t>(f.data, 1);
+    put_le<uint32_t>(f.data, 31);
+    put_le<uint8_t>(f.data, 1);
+    put_le<uint64_t>(f.data, sig.size());
+    uint64_t rows = 0;
+    for (uint64_t s : sig) {
+        f.fields.push_back({f.data.size(), 8});
+        put_le<uint64_t>(f.data, s);
+        f.fields.push_back({f.data.size(), 8});
+        put_le<uint64_t>(f.data, 3);
+        rows += s;
+    }
+    f.fields.push_back({f.data.size(), 8});
+    put_le<uint64_t>(f.data, page);
+    f.fields.push_back({f.data.size(), 4});
+    put_le<uint32_t>(f.data, docs);
+    for (uint32_t i = 0; i < docs; ++i) f.data += "a" + std::to_string(i) + "\n";
+    f.data += "COMPACT_INDEX";
+    f.data.append((page - f.data.size() % page) % page, '\0');
+    f.header = f.data.size();
+    f.data += rand_seq(rows * page, "ACGT\n\x01\xff");
+    return f;
+}
+
+static int fuzz_bank_headers(int* cases, int* refused) {
+    int bad = 0;
+    const std::string path = "/tmp/xs_asan_bank.bin";
+    auto read_one = [&](const BankFile& f, const std::string& data, int want /* 1 ok, 0 refused, -1 either */) {
+        write_file(path, data);
+        xs::BankGeometry g;
+        std::string err;
+        const int rc = xs::read_bank_header(path.c_str(), f.kind, &g, &err);
+        ++*cases;
+        if (rc) ++*refused;
+        bool ok = rc == XS_OK || rc == XS_ERR_FORMAT || rc == XS_ERR_UNSUPPORTED;
+        if (rc != XS_OK && err.empty()) ok = false;
+        if (rc == XS_OK) {  // in 128 bits: the sizes multiply out to the bytes the file holds
+            const unsigned __int128 rows = g.sig_total;
+            unsigned __int128 sum = 0;
+            for (uint64_t s : g.sig) sum += s;
+            if (f.kind == XS_BANK_RBLOOM) ok = ok && g.payload_bytes == data.size() - 8 && g.dev_bytes >= g.nbytes + 16;
+            else
+                ok = ok && sum == rows && rows * g.page == data.size() - g.payload_offset &&
+                     rows * g.pitch == g.dev_bytes && g.names.size() == g.D && g.sig.size() == g.G && g.h <= 16;
+        }
+        if (want >= 0 && (rc == XS_OK) != (want == 1)) ok = false;
+        if (!ok && bad++ < 10) fprintf(stderr, "bank header: kind %d, %zu bytes: rc %d (%s)\n", f.kind, data.size(), rc, err.c_str());
+    };
+    std::vector<BankFile> files{classic_file(64, 257), classic_file(100, 101), compact_file(150, {37, 11, 23}, 8, false),
+                                compact_file(1430, {5, 3, 4}, 64, true)};
+    {
+        BankFile r{XS_BANK_RBLOOM, std::string(), {{0, 8}}, 8, false};
+        put_le<uint64_t>(r.data, 7);
+        r.data += rand_seq(1000, "ACGT\n\x01\xff");
+        files.push_back(r);
+    }
+    for (const BankFile& f : files) {
+        read_one(f, f.data, 1);
+        for (size_t n = 0; n < f.data.size(); ++n)  // an rbloom file carries no length: a cut past K is a smaller filter
+            read_one(f, f.data.substr(0, n), f.kind == XS_BANK_RBLOOM ? (n > 8 ? 1 : 0) : 0);
+        std::vector<size_t> flip;
+        if (f.flip_fields_only) {
+            for (auto fl : f.fields)
+                for (size_t b = fl.first; b < fl.first + fl.second; ++b) flip.push_back(b);
+        } else {
+            for (size_t b = 0; b < f.header; ++b) flip.push_back(b);
+        }
+        for (size_t b : flip)
+            for (int bit = 0; bit < 8; ++bit) {
+                std::string d = f.data;
+                d[b] = (char)(d[b] ^ (1 << bit));
+                read_one(f, d, -1);
+            }
+        for (auto fl : f.fields) {
+            uint64_t v = 0;
+            memcpy(&v, f.data.data() + fl.first, fl.second);
+            for (uint64_t nv : {uint64_t(0), uint64_t(1), v - 1, v + 1, uint64_t(1) << 31, (uint64_t(1) << 32) - 1,
+                                (uint64_t(1) << 32) + v, (uint64_t(1) << 61) + v, uint64_t(1) << 63, ~uint64_t(0)}) {
+                if (fl.second < 8 && nv >> (8 * fl.second)) continue;  // as far as the field is wide
+                std::string d = f.data;
+                memcpy(&d[fl.first], &nv, fl.second);
+                read_one(f, d, -1);
+            }
+        }
+        for (int trial = 0; trial < 400; ++trial) {  // splices: random bytes over the header, pieces cut out or doubled
+            std::string d = f.data;
+            const size_t at = rng() % (f.header + 1), n = 1 + rng() % 16;
+            switch (rng() % 3) {
+                case 0:
+                    for (size_t i = at; i < std::min(d.size(), at + n); ++i) d[i] = (char)(rng() % 256);
+                    break;
+                case 1: d.erase(at, n); break;
+                default: d.insert(at, d.substr(at, n));
+            }
+            read_one(f, d, -1);
+        }
+    }
+    // arguments: sizes beyond 64 bits are XS_ERR_ARG, never a wrapped geometry
+    auto args = [&](int kind, uint64_t D, uint64_t G, uint64_t page, std::vector<uint64_t> sig, uint64_t nbytes, int want) {
+        xs::BankGeometry g;
+        g.kind = kind;
+        g.k = 21;
+        g.h = 7;
+        g.D = D;
+        g.G = G;
+        g.page = page;
+        g.sig = sig;
+        g.nbytes = nbytes;
+        std::string err;
+        const int rc = xs::check_geometry(&g, xs::GeometrySource::kArguments, &err);
+        ++*cases;
+        if (rc) ++*refused;
+        if (rc != want && bad++ < 10) fprintf(stderr, "bank geometry: rc %d, expected %d (%s)\n", rc, want, err.c_str());
+    };
+    const uint64_t top = ~uint64_t(0);
+    args(XS_BANK_COBS_CLASSIC, 64, 1, 8, {257}, 0, XS_OK);
+    args(XS_BANK_COBS_CLASSIC, 64, 1, 8, {uint64_t(1) << 61}, 0, XS_ERR_ARG);
+    args(XS_BANK_COBS_CLASSIC, 64, 1, 8, {uint64_t(1) << 60}, 0, XS_ERR_ARG);
+    args(XS_BANK_COBS_COMPACT, 150, 3, 8, {uint64_t(1) << 63, uint64_t(1) << 63, 5}, 0, XS_ERR_ARG);
+    args(XS_BANK_COBS_COMPACT, 150, uint64_t(1) << 61, 8, {5, 3, 4}, 0, XS_ERR_ARG);
+    args(XS_BANK_COBS_COMPACT, 150, 3, uint64_t(1) << 61, {5, 3, 4}, 0, XS_ERR_ARG);
+    args(XS_BANK_COBS_COMPACT, 150, top, top, {5, 3, 4}, 0, XS_ERR_ARG);
+    args(XS_BANK_COBS_COMPACT, top, 1, top / 8 + 1, {5}, 0, XS_ERR_ARG);
+    args(XS_BANK_COBS_COMPACT, 150, 2, 8, {5, 3}, 0, XS_ERR_FORMAT);
+    args(XS_BANK_RBLOOM, 1, 0, 0, {}, 1000, XS_OK);
+    args(XS_BANK_RBLOOM, 1, 0, 0, {}, uint64_t(1) << 61, XS_ERR_ARG);
+    args(XS_BANK_RBLOOM, 1, 0, 0, {}, top, XS_ERR_ARG);
+    args(XS_BANK_RBLOOM, 1, 0, 0, {}, 0, XS_ERR_FORMAT);
+    return bad;
+}
+
 int main() {
     const std::string path = "/tmp/xs_asan_in.txt";
     int files = 0, errors = 0, unexpected = 0;
@@ -408,9 +578,11 @@ int main() {
     }
     int plans = 0;
     unexpected += fuzz_mlst_plan(&plans);
-    printf("host sanitizer run: %d MLST contig plans; %d input files x 15 reader configurations + 12 byte-range parts, 20 JSON matrices, "
+    int bank_cases = 0, bank_refused = 0;
+    unexpected += fuzz_bank_headers(&bank_cases, &bank_refused);
+    printf("host sanitizer run: %d bank file headers and geometries (%d refused with a code); %d MLST contig plans; %d input files x 15 reader configurations + 12 byte-range parts, 20 JSON matrices, "
            "20 id-key batches + a threaded one, 6 member masks, 6 threaded repeat checks, 1800 worker-pool jobs from 6 threads (nested, throwing); %d clean error returns, "
            "%d unexpected results\n",
-           plans, files, errors, unexpected);
+           bank_cases, bank_refused, plans, files, errors, unexpected);
     return unexpected ? 1 : 0;
 }

@@ -133,6 +133,8 @@ SIGNATURES = {
     "xs_device_count": (_int, [ctypes.POINTER(_int)]),
     "xs_bank_open": (_int, [ctypes.c_char_p, _int, _int, _pp]),
     "xs_bank_open_docs": (_int, [ctypes.c_char_p, _int, _u64, _u64, _pp]),
+    "xs_bank_file_info": (_int, [ctypes.c_char_p, _int, ctypes.POINTER(BankInfo), ctypes.POINTER(_u64)]),
+    "xs_bank_file_names": (_int, [ctypes.c_char_p, _int, _vp, _u64, ctypes.POINTER(_u64)]),
     "xs_bank_create_cobs": (_int, [_int, _int, _u32, _u32, _u64, _u64, _u64, _vp, _vp, _pp]),
     "xs_bank_create_bloom": (_int, [_int, _u32, _u64, _u32, _pp]),
     "xs_bank_build": (_int, [_vp, _vp, _vp, _vp, _u64]),

@@ -200,6 +200,26 @@ class Bank:
             check(load().xs_bank_set_term_size(h, term_size))
         return bank
 
+    @staticmethod
+    def file_info(path: str | Path, kind: int, names: bool = False):
+        """(BankInfo, payload offset) of an index file from its header alone
+        (xs_bank_file_info): no device work, ``device`` is -1, and
+        ``device_bytes`` is the HBM an open would allocate.  The header is
+        checked as ``open`` checks it: a file refused here (XsError) is refused
+        there with the same code.  A classic index of more docs than one handle
+        takes (8192) is reported here and opens only in doc slices.  names=True: (BankInfo, payload offset, doc
+        names as bytes)."""
+        inf, off = BankInfo(), ctypes.c_uint64(0)
+        p = str(path).encode()
+        check(load().xs_bank_file_info(p, kind, ctypes.byref(inf), ctypes.byref(off)))
+        if not names:
+            return inf, int(off.value)
+        need = ctypes.c_uint64(0)
+        check(load().xs_bank_file_names(p, kind, None, 0, ctypes.byref(need)))
+        buf = ctypes.create_string_buffer(max(1, need.value))
+        check(load().xs_bank_file_names(p, kind, buf, need.value, ctypes.byref(need)))
+        return inf, int(off.value), buf.raw[:need.value].split(b"\n")[:-1]
+
     @classmethod
     def create_cobs(cls, term_size: int, num_hashes: int, signature_sizes: Sequence[int],
                     num_docs: int, doc_names: Sequence[str] | None = None,

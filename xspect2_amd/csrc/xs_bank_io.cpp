@@ -1,5 +1,7 @@
 // xs_bank_io.cpp — bank files and device residency: the COBS / rbloom file formats, the device image, payloads
 // streamed between files and the device through a ring of pinned slots, the open / create / save entry points.
+// Headers are read, and every geometry checked, by xs_bank_header.cpp (host only, no HIP): what it refuses is
+// refused before a handle exists and before the first HIP call here.
 //
 // Bank file layouts (restated; COBS and rbloom are not available offline, see
 // DESIGN.md "Oracle" — parity with their real files is unpinned):
@@ -25,6 +27,7 @@
 #include <fstream>
 #include <memory>
 
+#include "xs_bank_header.h"
 #include "xs_host.h"
 
 using namespace xs;
@@ -34,43 +37,54 @@ namespace {
 const char kClassicMagic[] = "CLASSIC_INDEX";
 const char kCompactMagic[] = "COMPACT_INDEX";
 
-int validate_geometry(xs_bank* b) {
-    if (b->k < 1 || b->k > kMaxK)
-        return fail(XS_ERR_UNSUPPORTED, "term_size %u unsupported on the device (1..%u)", b->k, kMaxK);
-    if (b->h < 1 || b->h > kMaxHashes)
-        return fail(XS_ERR_UNSUPPORTED, "num_hashes %u unsupported on the device (1..%u)", b->h,
-                    kMaxHashes);
-    if (b->kind == XS_BANK_RBLOOM) {
-        if (b->nbytes == 0) return fail(XS_ERR_FORMAT, "empty rbloom filter");
-        return XS_OK;
-    }
-    if (b->D == 0) return fail(XS_ERR_FORMAT, "bank has no documents");
-    if (b->page == 0 || b->G == 0 || b->sig.size() != b->G)
-        return fail(XS_ERR_FORMAT, "bad group geometry");
-    if (b->G * 8 * b->page < b->D || (b->G - 1) * 8 * b->page >= b->D)
-        return fail(XS_ERR_FORMAT, "groups (%llu x %llu bytes) do not match %llu docs",
-                    (unsigned long long)b->G, (unsigned long long)b->page,
-                    (unsigned long long)b->D);
-    for (auto s : b->sig)
-        if (s == 0) return fail(XS_ERR_FORMAT, "zero signature size");
-    // Device row pitch: 16, 32, 64 or a multiple of 128 bytes, so that no row
-    // straddles a 128-byte line (a 48-byte pitch made 2 rows in 8 cost two
-    // line fills).  The kernels load only the (page + 15) / 16 data chunks.
-    const uint64_t p16 = (b->page + 15) / 16 * 16;
-    b->pitch = p16 <= 64 ? (p16 <= 16 ? 16 : p16 <= 32 ? 32 : 64) : (p16 + 127) / 128 * 128;
+// The device's limits as the header unit restates them.
+static_assert(kHeaderMaxK == kMaxK && kHeaderMaxHashes == kMaxHashes, "xs_bank_header.h and xs_internal.h disagree");
+
+// a refusal of the header unit as the calling thread's error; `path` names the file, if any
+int refused(int rc, const char* path, const std::string& err) {
+    return path ? fail(rc, "%s: %s", path, err.c_str()) : fail(rc, "%s", err.c_str());
+}
+
+// The LDS counters of a probe block hold every doc of the bank (after the header unit's checks).
+int check_lds_budget(uint64_t D, const char* path) {
     int wpb;
     size_t lds;
-    if (probe_blocks(b->D, &wpb, &lds) != 0)
-        return fail(XS_ERR_UNSUPPORTED, "%llu documents exceed the LDS counter budget",
-                    (unsigned long long)b->D);
+    if (D > UINT32_MAX || probe_blocks(D, &wpb, &lds) != 0)
+        return refused(XS_ERR_UNSUPPORTED, path,
+                       std::to_string((unsigned long long)D) + " documents exceed the LDS counter budget");
     return XS_OK;
 }
 
-// Allocate the (zeroed) device image and group table.
+// The header of `path`, read and checked on the host alone (xs_bank_header.h): the file's layout, not yet
+// whether one handle can hold all its docs (check_lds_budget, which xs_bank_open applies to the whole bank and
+// xs_bank_open_docs to its slice only).
+int read_checked_header(const char* path, int kind, BankGeometry* g) {
+    std::string err;
+    if (int rc = read_bank_header(path, kind, g, &err)) return refused(rc, path, err);
+    return XS_OK;
+}
+
+// A handle of a checked geometry (its names moved out of g); no device work yet.
+std::unique_ptr<xs_bank> bank_of(int device, BankGeometry& g) {
+    auto b = std::make_unique<xs_bank>(device, g.kind);
+    b->k = g.k;
+    b->h = (uint32_t)g.h;  // 1..kMaxHashes
+    b->canonicalize = g.canonicalize;
+    b->D = g.D;
+    b->G = g.G;
+    b->page = g.page;
+    b->sig = g.sig;
+    b->names = std::move(g.names);
+    b->nbytes = g.nbytes;
+    b->pitch = g.pitch;
+    b->dev_bytes = g.dev_bytes;
+    return b;
+}
+
+// Allocate the (zeroed) device image (b->dev_bytes, from the checked geometry) and group table.
 int alloc_image(xs_bank* b) {
     HIPCHK(hipSetDevice(b->device));
     if (!b->stream) HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    b->dev_bytes = b->kind == XS_BANK_RBLOOM ? (b->nbytes + 15) / 16 * 16 + 16 : b->sig_total() * b->pitch;
     if (int rc = b->image.ensure(b->dev_bytes)) return rc;
     HIPCHK(hipMemsetAsync(b->image.p, 0, b->dev_bytes, b->stream));
     if (b->kind != XS_BANK_RBLOOM) {
@@ -307,90 +321,10 @@ int upload_file_payload(xs_bank* b, const char* path, uint64_t pos) {
     return XS_OK;
 }
 
-// ---- little binary reader -------------------------------------------------
-struct Reader {
-    std::ifstream f;
-    bool ok = true;
-    uint64_t fsize = 0;
-    bool open(const char* path) {  // false: `path` cannot be opened
-        f.open(path, std::ios::binary);
-        if (!f) return false;
-        f.seekg(0, std::ios::end);
-        fsize = (uint64_t)f.tellg();
-        f.seekg(0);
-        return true;
-    }
-    template <class T>
-    T get() {
-        T v{};
-        f.read(reinterpret_cast<char*>(&v), sizeof(T));
-        if (!f) ok = false;
-        return v;
-    }
-    bool expect(const char* s) {
-        std::string got(strlen(s), '\0');
-        f.read(&got[0], (std::streamsize)got.size());
-        if (!f || got != s) ok = false;
-        return ok;
-    }
-    std::string line() {
-        std::string s;
-        if (!std::getline(f, s)) ok = false;
-        return s;
-    }
-};
-
+// ---- writers -----------------------------------------------------------------
 template <class T>
 void put(std::ofstream& o, T v) {
     o.write(reinterpret_cast<const char*>(&v), sizeof(T));
-}
-
-int read_cobs_header(xs_bank* b, Reader& rd, const char* path) {
-    if (!rd.expect("COBS:")) return fail(XS_ERR_FORMAT, "%s: not a COBS index", path);
-    if (b->kind == XS_BANK_COBS_CLASSIC) {
-        if (!rd.expect(kClassicMagic)) return fail(XS_ERR_FORMAT, "%s: not a classic index", path);
-        const uint32_t ver = rd.get<uint32_t>();
-        const uint32_t nd = rd.get<uint32_t>();
-        b->k = rd.get<uint32_t>();
-        b->canonicalize = rd.get<uint8_t>();
-        const uint64_t s = rd.get<uint64_t>();
-        b->h = (uint32_t)rd.get<uint64_t>();
-        if (!rd.ok || ver != 1) return fail(XS_ERR_FORMAT, "%s: bad classic header", path);
-        b->D = nd;
-        b->G = 1;
-        b->page = (nd + 7) / 8;
-        b->sig.assign(1, s);
-        for (uint32_t i = 0; i < nd; ++i) b->names.push_back(rd.line());
-        if (!rd.expect(kClassicMagic)) return fail(XS_ERR_FORMAT, "%s: bad classic trailer", path);
-    } else {
-        if (!rd.expect(kCompactMagic)) return fail(XS_ERR_FORMAT, "%s: not a compact index", path);
-        const uint32_t ver = rd.get<uint32_t>();
-        b->k = rd.get<uint32_t>();
-        b->canonicalize = rd.get<uint8_t>();
-        const uint64_t G = rd.get<uint64_t>();
-        if (!rd.ok || ver != 1 || G == 0 || G > (1u << 20))
-            return fail(XS_ERR_FORMAT, "%s: bad compact header", path);
-        b->G = G;
-        for (uint64_t g = 0; g < G; ++g) {
-            b->sig.push_back(rd.get<uint64_t>());
-            const uint32_t hg = (uint32_t)rd.get<uint64_t>();
-            if (g == 0) b->h = hg;
-            else if (hg != b->h) return fail(XS_ERR_FORMAT, "%s: mixed num_hashes", path);
-        }
-        b->page = rd.get<uint64_t>();
-        const uint32_t nd = rd.get<uint32_t>();
-        b->D = nd;
-        for (uint32_t i = 0; i < nd; ++i) b->names.push_back(rd.line());
-        if (!rd.expect(kCompactMagic)) return fail(XS_ERR_FORMAT, "%s: bad compact trailer", path);
-        if (b->page == 0) return fail(XS_ERR_FORMAT, "%s: zero page size", path);
-        const uint64_t pos = (uint64_t)rd.f.tellg();
-        const uint64_t pad = (b->page - pos % b->page) % b->page;
-        rd.f.seekg((std::streamoff)(pos + pad));
-    }
-    if (!rd.ok) return fail(XS_ERR_FORMAT, "%s: truncated header", path);
-    if (b->canonicalize != 1)
-        return fail(XS_ERR_UNSUPPORTED, "%s: non-canonical COBS indices are not supported", path);
-    return XS_OK;
 }
 
 int write_cobs_file(xs_bank* b, const char* path) {
@@ -452,29 +386,61 @@ int xs_bank_open(const char* path, int kind, int device, xs_bank** out) {
         *out = nullptr;
         if (kind != XS_BANK_COBS_CLASSIC && kind != XS_BANK_COBS_COMPACT && kind != XS_BANK_RBLOOM)
             return fail(XS_ERR_ARG, "unknown bank kind %d", kind);
-        Reader rd;
-        if (!rd.open(path)) return fail(XS_ERR_IO, "cannot open %s", path);
-        auto b = std::make_unique<xs_bank>(device, kind);
-        if (kind == XS_BANK_RBLOOM) {
-            b->h = (uint32_t)rd.get<uint64_t>();
-            if (!rd.ok || rd.fsize <= 8) return fail(XS_ERR_FORMAT, "%s: truncated rbloom file", path);
-            b->nbytes = rd.fsize - 8;
-            b->D = 1;
-            b->names.push_back("0");
-            // An rbloom file carries no k (the model JSON does); default to XspecT's
-            // k = 21 (train.py:167-174) until xs_bank_set_term_size overrides it.
-            b->k = 21;
-        } else if (int rc = read_cobs_header(b.get(), rd, path)) {
-            return rc;
-        }
-        if (int rc = validate_geometry(b.get())) return rc;
-        const uint64_t pos = (uint64_t)rd.f.tellg();
-        if (rd.fsize - pos != b->payload_bytes())
-            return fail(XS_ERR_FORMAT, "%s: payload is %llu bytes, header implies %llu", path,
-                        (unsigned long long)(rd.fsize - pos), (unsigned long long)b->payload_bytes());
+        BankGeometry g;
+        if (int rc = read_checked_header(path, kind, &g)) return rc;  // before any HIP call
+        if (kind != XS_BANK_RBLOOM)
+            if (int rc = check_lds_budget(g.D, path)) return rc;
+        auto b = bank_of(device, g);
         if (int rc = alloc_image(b.get())) return rc;
-        if (int rc = upload_file_payload(b.get(), path, pos)) return rc;
+        if (int rc = upload_file_payload(b.get(), path, g.payload_offset)) return rc;
         *out = b.release();
+        return XS_OK;
+    });
+}
+
+int xs_bank_file_info(const char* path, int kind, xs_bank_info_t* out, uint64_t* payload_offset) {
+    return xs::guard([&]() -> int {
+        if (!path || !out) return fail(XS_ERR_ARG, "null argument");
+        memset(out, 0, sizeof(*out));
+        if (payload_offset) *payload_offset = 0;
+        if (kind != XS_BANK_COBS_CLASSIC && kind != XS_BANK_COBS_COMPACT && kind != XS_BANK_RBLOOM)
+            return fail(XS_ERR_ARG, "unknown bank kind %d", kind);
+        BankGeometry g;
+        if (int rc = read_checked_header(path, kind, &g)) return rc;
+        out->kind = kind;
+        out->device = -1;
+        out->term_size = g.k;
+        out->num_hashes = (uint32_t)g.h;
+        out->canonicalize = g.canonicalize;
+        out->num_docs = g.D;
+        out->num_groups = kind == XS_BANK_RBLOOM ? 0 : g.G;
+        out->page_size = g.page;
+        out->signature_rows = g.sig_total;
+        out->bloom_bits = kind == XS_BANK_RBLOOM ? g.nbytes * 8 : 0;
+        out->device_bytes = g.dev_bytes;
+        out->device_row_pitch = g.pitch;
+        if (payload_offset) *payload_offset = g.payload_offset;
+        return XS_OK;
+    });
+}
+
+int xs_bank_file_names(const char* path, int kind, char* buf, uint64_t cap, uint64_t* bytes) {
+    return xs::guard([&]() -> int {
+        if (!path || !bytes || (cap && !buf)) return fail(XS_ERR_ARG, "null argument");
+        *bytes = 0;
+        if (kind != XS_BANK_COBS_CLASSIC && kind != XS_BANK_COBS_COMPACT && kind != XS_BANK_RBLOOM)
+            return fail(XS_ERR_ARG, "unknown bank kind %d", kind);
+        BankGeometry g;
+        if (int rc = read_checked_header(path, kind, &g)) return rc;
+        uint64_t need = 0;
+        for (auto& n : g.names) need += n.size() + 1;
+        *bytes = need;
+        if (need > cap) return XS_OK;  // the caller asks again with room for *bytes
+        for (auto& n : g.names) {
+            memcpy(buf, n.data(), n.size());
+            buf[n.size()] = '\n';
+            buf += n.size() + 1;
+        }
         return XS_OK;
     });
 }
@@ -483,28 +449,28 @@ int xs_bank_open_docs(const char* path, int device, uint64_t doc_lo, uint64_t do
     return xs::guard([&]() -> int {
         if (!path || !out) return fail(XS_ERR_ARG, "null argument");
         *out = nullptr;
-        Reader rd;
-        if (!rd.open(path)) return fail(XS_ERR_IO, "cannot open %s", path);
-        auto full = std::make_unique<xs_bank>(device, XS_BANK_COBS_CLASSIC);
-        if (int rc = read_cobs_header(full.get(), rd, path)) return rc;
-        const uint64_t D = full->D, R = full->page, S = full->sig[0];
+        // the whole file's header, payload size included, as xs_bank_file_info checks it; only the slice has to
+        // meet the LDS budget (the split exists for banks of more docs than one handle takes)
+        BankGeometry full;
+        std::string err;
+        if (int rc = read_checked_header(path, XS_BANK_COBS_CLASSIC, &full)) return rc;
+        const uint64_t D = full.D, R = full.page, S = full.sig[0], pos = full.payload_offset;
         if (doc_lo % 8 || doc_lo >= doc_hi || doc_hi > D || (doc_hi % 8 && doc_hi != D))
             return fail(XS_ERR_ARG, "doc range [%llu, %llu) of %llu docs: bounds must be multiples of 8 (or the end)",
                         (unsigned long long)doc_lo, (unsigned long long)doc_hi, (unsigned long long)D);
-        const uint64_t pos = (uint64_t)rd.f.tellg();
-        if (rd.fsize - pos != S * R)
-            return fail(XS_ERR_FORMAT, "%s: payload is %llu bytes, header implies %llu", path,
-                        (unsigned long long)(rd.fsize - pos), (unsigned long long)(S * R));
-        auto b = std::make_unique<xs_bank>(device, XS_BANK_COBS_CLASSIC);
-        b->k = full->k;
-        b->h = full->h;
-        b->canonicalize = full->canonicalize;
-        b->D = doc_hi - doc_lo;
-        b->G = 1;
-        b->page = (b->D + 7) / 8;
-        b->sig.assign(1, S);
-        b->names.assign(full->names.begin() + (ptrdiff_t)doc_lo, full->names.begin() + (ptrdiff_t)doc_hi);
-        if (int rc = validate_geometry(b.get())) return rc;
+        BankGeometry g;
+        g.kind = XS_BANK_COBS_CLASSIC;
+        g.k = full.k;
+        g.h = full.h;
+        g.canonicalize = full.canonicalize;
+        g.D = doc_hi - doc_lo;
+        g.G = 1;
+        g.page = (g.D + 7) / 8;
+        g.sig.assign(1, S);
+        g.names.assign(full.names.begin() + (ptrdiff_t)doc_lo, full.names.begin() + (ptrdiff_t)doc_hi);
+        if (int rc = check_geometry(&g, GeometrySource::kFile, &err)) return refused(rc, path, err);
+        if (int rc = check_lds_budget(g.D, path)) return rc;
+        auto b = bank_of(device, g);
         if (int rc = alloc_image(b.get())) return rc;
         // whole rows to the device a piece at a time (about kLoadPiece bytes of whole rows), each
         // piece's byte columns [doc_lo / 8, + page) repacked into the image at its first row: the
@@ -538,18 +504,29 @@ int xs_bank_create_cobs(int device, int kind, uint32_t term_size, uint32_t num_h
         *out = nullptr;
         if (kind != XS_BANK_COBS_CLASSIC && kind != XS_BANK_COBS_COMPACT)
             return fail(XS_ERR_ARG, "kind must be a COBS kind");
-        if (kind == XS_BANK_COBS_CLASSIC && (num_groups != 1 || page_size != (num_docs + 7) / 8))
+        if (kind == XS_BANK_COBS_CLASSIC && (num_groups != 1 || page_size != num_docs / 8 + (num_docs % 8 != 0)))
             return fail(XS_ERR_ARG, "classic banks have one group of ceil(D/8) bytes");
-        auto b = std::make_unique<xs_bank>(device, kind);
-        b->k = term_size;
-        b->h = num_hashes;
-        b->D = num_docs;
-        b->G = num_groups;
-        b->page = page_size;
-        b->sig.assign(sig, sig + num_groups);
-        for (uint64_t i = 0; i < num_docs; ++i)
-            b->names.push_back(doc_names ? std::string(doc_names[i]) : std::to_string(i));
-        if (int rc = validate_geometry(b.get())) return rc;
+        // the geometry is checked before sig's num_groups entries and the names are touched
+        BankGeometry g;
+        g.kind = kind;
+        g.k = term_size;
+        g.h = num_hashes;
+        g.D = num_docs;
+        g.G = num_groups;
+        g.page = page_size;
+        std::string err;
+        if (int rc = check_term_and_hashes(g.k, g.h, &err)) return refused(rc, nullptr, err);
+        if (int rc = check_cobs_shape(num_docs, num_groups, page_size, GeometrySource::kArguments, &err))
+            return refused(rc, nullptr, err);
+        if (int rc = check_lds_budget(num_docs, nullptr)) return rc;  // bounds the docs, and so the groups
+        g.sig.assign(sig, sig + num_groups);
+        if (int rc = check_geometry(&g, GeometrySource::kArguments, &err)) return refused(rc, nullptr, err);
+        g.names.reserve((size_t)num_docs);
+        for (uint64_t i = 0; i < num_docs; ++i) {
+            if (doc_names && !doc_names[i]) return fail(XS_ERR_ARG, "doc_names[%llu] is NULL", (unsigned long long)i);
+            g.names.push_back(doc_names ? std::string(doc_names[i]) : std::to_string(i));
+        }
+        auto b = bank_of(device, g);
         if (int rc = alloc_image(b.get())) return rc;
         *out = b.release();
         return XS_OK;
@@ -561,13 +538,16 @@ int xs_bank_create_bloom(int device, uint32_t term_size, uint64_t nbytes, uint32
     return xs::guard([&]() -> int {
         if (!out) return fail(XS_ERR_ARG, "null argument");
         *out = nullptr;
-        auto b = std::make_unique<xs_bank>(device, XS_BANK_RBLOOM);
-        b->k = term_size;
-        b->h = nhash;
-        b->nbytes = nbytes;
-        b->D = 1;
-        b->names.push_back("0");
-        if (int rc = validate_geometry(b.get())) return rc;
+        BankGeometry g;
+        g.kind = XS_BANK_RBLOOM;
+        g.k = term_size;
+        g.h = nhash;
+        g.nbytes = nbytes;
+        g.D = 1;
+        g.names.push_back("0");
+        std::string err;
+        if (int rc = check_geometry(&g, GeometrySource::kArguments, &err)) return refused(rc, nullptr, err);
+        auto b = bank_of(device, g);
         if (int rc = alloc_image(b.get())) return rc;
         *out = b.release();
         return XS_OK;

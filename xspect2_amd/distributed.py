@@ -665,13 +665,15 @@ def classify_docs_sharded(model, input_file: Path, output_path: Path, step: int 
 
 
 def cobs_classic_docs(index_path: Path) -> int:
-    """Document count of a classic COBS index, from its header (magic, u32
-    version, u32 docs; the layout xs_bank_open reads)."""
-    with open(index_path, "rb") as fh:
-        head = fh.read(26)
-    if not head.startswith(b"COBS:CLASSIC_INDEX") or len(head) < 26:
-        raise ValueError(f"{index_path}: not a classic COBS index")
-    return int.from_bytes(head[22:26], "little")
+    """Document count of a classic COBS index, from its header as the library
+    reads and checks it (xs_bank_file_info; the layout of DESIGN.md §4b A6).
+    ValueError for a file that is not a whole classic index."""
+    from ._lib import XS_BANK_COBS_CLASSIC, XsError
+    from .bank import Bank
+    try:
+        return int(Bank.file_info(index_path, XS_BANK_COBS_CLASSIC)[0].num_docs)
+    except XsError as e:
+        raise ValueError(f"{index_path}: not a classic COBS index ({e})") from e
 
 
 def doc_slice(num_docs: int, rank: int, world: int) -> tuple[int, int]:
