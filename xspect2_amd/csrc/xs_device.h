@@ -527,45 +527,37 @@ inline size_t slots_lds(const CobsView& bv) { return (size_t)((bv.D + 127) / 128
 
 // ---- COBS probe families (one translation unit each) ---------------------
 // Every family keeps its compiled instantiations in one {name, function} table
-// that its picker indexes: a launcher reports (through `kernel`, when given)
-// the name of the entry it launched, and *_kernel_names lists the same table.
+// that its picker indexes: its grid and its launcher go through the picker, the
+// launcher reports (through `kernel`, when given) the name of the entry it
+// launched, and its names lists the same table.
 template <class Fn>
 struct ProbeKernel {
     const char* name;  // as xs_bank_probe_kernel reports it; nullptr: a table slot with no instantiation
     Fn fn;
+    mutable std::atomic<int> cached{0};  // resident grid of fn, from the first query
+    int grid(int threads, size_t lds) const {
+        return cached_grid(cached, [&] { return resident_grid(fn, threads, lds); });
+    }
 };
 template <class Fn, size_t N>
 static void table_names(const ProbeKernel<Fn> (&table)[N], std::string& out) {
     for (const ProbeKernel<Fn>& e : table)
         if (e.name) out.append(e.name).append("\n");
 }
-// xs_probe_fast.hip: classic D <= 128, species (21, 7) / MLST (31, 1)
-bool cobs_fast(const CobsView& bv, uint32_t k);
-int grid_cobs_fast(uint32_t k);
-hipError_t launch_cobs_fast(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                            int blocks, hipStream_t s, const char** kernel = nullptr);
-void fast_kernel_names(std::string& out);
-// xs_probe_wide.hip: classic rows of 2..16 chunks (0 = not taken)
-int wide_for(const CobsView& bv);
-int grid_cobs_wide(const CobsView& bv, uint32_t k);
-hipError_t launch_cobs_wide(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                            int blocks, hipStream_t s, const char** kernel = nullptr);
-void wide_kernel_names(std::string& out);
-// xs_probe_vslice.hip: one hash, 1-4 groups of 64-byte pages (MLST loci)
-bool vslice_take(const CobsView& bv);
-int grid_cobs_vslice(const CobsView& bv, uint32_t k);
-hipError_t launch_cobs_vslice(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                              int blocks, hipStream_t s, const char** kernel = nullptr);
-void vslice_kernel_names(std::string& out);
-// xs_probe_slots.hip: compile-time group x chunk layouts (false = not taken)
-bool slots_take(const CobsView& bv);
-int grid_cobs_slots(const CobsView& bv, uint32_t k);
-hipError_t launch_cobs_slots(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                             int blocks, hipStream_t s, const char** kernel = nullptr);
-void slots_kernel_names(std::string& out);
-// xs_probe_general.hip: anything the LDS counters hold
-int grid_cobs_general(const CobsView& bv);
-hipError_t launch_cobs_general(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                               int blocks, hipStream_t s, const char** kernel = nullptr);
+
+// What the router (xs_kernels.hip: kCobsFamilies) asks of a family.  grid and
+// launch are called only for banks that take accepts.
+struct CobsFamily {
+    bool (*take)(const CobsView& bv, uint32_t k);
+    int (*grid)(const CobsView& bv, uint32_t k);  // partials are sized by it
+    hipError_t (*launch)(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials, int blocks,
+                         hipStream_t s, const char** kernel);
+    void (*names)(std::string& out);
+};
+const CobsFamily& fast_family();     // xs_probe_fast.hip: classic D <= 128, species (21, 7) / MLST (31, 1)
+const CobsFamily& vslice_family();   // xs_probe_vslice.hip: one hash, 1-4 groups of 64-byte pages (MLST loci)
+const CobsFamily& wide_family();     // xs_probe_wide.hip: classic rows of 2..16 chunks, compact 2..4 x 2..4
+const CobsFamily& slots_family();    // xs_probe_slots.hip: compile-time group x chunk layouts
+const CobsFamily& general_family();  // xs_probe_general.hip: anything the LDS counters hold
 
 }  // namespace xs

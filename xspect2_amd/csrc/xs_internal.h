@@ -75,7 +75,7 @@ struct ReadView {
     uint32_t grab = 4;         // units a wave takes from the queue per atomic (small calls: 1)
 };
 
-// ---- launchers (xs_kernels.hip) -------------------------------------------
+// ---- launchers (xs_kernels.hip; launch_probe_bloom and probe_grid_bloom: xs_probe_bloom.hip) ----
 // k-mers sampled every `step` positions from a read of `len` bytes: units_kernel's formula, and the
 // host's wherever it needs the count without the device.
 __host__ __device__ inline uint64_t sampled_kmers(uint64_t len, uint32_t k, uint32_t step) {

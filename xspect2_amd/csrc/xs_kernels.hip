@@ -1,4 +1,5 @@
-// xs_kernels.hip — gfx950 (MI355X, CDNA4) kernels of the k-mer x filter probe path.
+// xs_kernels.hip — gfx950 (MI355X, CDNA4) kernels around the k-mer x filter probes: the unit, scan and
+// scatter kernels, the routing of a COBS bank to its probe family, the bank builders and the small row kernels.
 //
 // Pipeline of one query call (reads already in HBM):
 //   units    : per-read sampled k-mer count and #units (segments of kSegKmers)
@@ -9,6 +10,9 @@
 //              rbloom), h random 16-byte row gathers from the bank, AND, and
 //              per-doc ballot/popcount counting into per-wave LDS counters
 //                                                   [HBM random-read bound]
+//              COBS: the first family of kCobsFamilies (below) that takes the bank,
+//              xs_probe_fast/vslice/wide/slots/general.hip; rbloom: xs_probe_bloom.hip;
+//              what they share is in xs_direct.h
 //   reduce   : per-block partial totals -> per-doc totals (u64)
 //
 // Reference semantics restated (see oracle/xs_oracle.c for the CPU version):
@@ -16,7 +20,7 @@
 //   rbloom `kmer in bf`                    probabilistic_single_filter_model.py:122-124
 #include <hipcub/hipcub.hpp>
 
-#include "xs_device.h"
+#include "xs_direct.h"
 
 namespace xs {
 
@@ -53,109 +57,6 @@ __global__ void scatter_units_kernel(const uint64_t* __restrict__ nseg,
     }
 }
 
-// ------------------------------------------------------------------ rbloom probe
-// Filter bits tested before the rest: 2 measured fastest for member-heavy
-// and foreign-heavy reads alike (all 7 at once: 15.69 against 13.43 ms per
-// config-2 step).
-constexpr int kBloomSplit = 2;
-// All K bit indices first, then all K dword loads in flight at once (the
-// reference stops at the first zero bit; the answer is the same).
-// Returns bit 0: member; bit 1: the second load phase ran.
-template <int KT, int KB, int SPLIT>
-__device__ __forceinline__ uint32_t bloom_member(const Kmer& c, uint32_t k, const BloomView& bv) {
-    constexpr int NK = KB ? KB : (int)kMaxHashes;
-    const uint32_t K = KB ? KB : bv.K;
-    uint64_t sl = xxh3_kmer<KT>(c, k), sh = 0;
-    uint64_t idx[NK];
-#pragma unroll
-    for (int j = 0; j < NK; ++j) {
-        if ((uint32_t)j < K) {
-            lcg_step(sl, sh);
-            idx[j] = fastmod(sh, bv.mbits, bv.magic);
-        }
-    }
-    // The first SPLIT bits decide most non-members (rbloom stops at the
-    // first zero bit); the other loads go out only for lanes still in.
-    // SPLIT = 0: all K loads at once.
-    uint32_t all = 1;
-#pragma unroll
-    for (int j = 0; j < NK; ++j)
-        if ((uint32_t)j < K && (SPLIT == 0 || j < SPLIT)) all &= bv.bits[idx[j] >> 5] >> (idx[j] & 31);
-    uint32_t phase2 = 0;
-    if (SPLIT != 0 && (all & 1u) && (uint32_t)SPLIT < K) {
-        phase2 = 2u;
-#pragma unroll
-        for (int j = SPLIT; j < NK; ++j)
-            if ((uint32_t)j < K) all &= bv.bits[idx[j] >> 5] >> (idx[j] & 31);
-    }
-    return (all & 1u) | phase2;
-}
-
-template <int KT, int KB, int SPLIT>
-__global__ void __launch_bounds__(kProbeThreads) probe_bloom_kernel(ReadView rv, BloomView bv,
-                                                                    uint32_t* __restrict__ hits,
-                                                                    uint64_t* __restrict__ partials) {
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int wpb = blockDim.x >> 6;
-    __shared__ uint64_t s_hits[kProbeThreads / kWave], s_kmers[kProbeThreads / kWave];
-    const uint32_t k = KT ? KT : rv.k;
-    const uint32_t step = rv.step;
-    const uint64_t U = rv.queue[0];
-    uint64_t hit_total = 0, kmer_total = 0, rows_total = 0;
-
-    for (;;) {
-        const uint64_t base = grab_units(rv.queue, lane, rv.grab);
-        if (base >= U) break;
-        const uint64_t uend = min(base + rv.grab, U);
-        for (uint64_t u = base; u < uend; ++u) {
-            const uint32_t r = rv.unit_read[u];
-            const uint64_t seg = u - rv.unit_ofs[r];
-            const uint64_t o0 = rv.offs[r];
-            const uint64_t len = rv.offs[r + 1] - o0;
-            const uint64_t nk = num_kmers(len, k, step);
-            const uint64_t t0 = seg * kSegKmers;
-            const uint32_t cnt = (uint32_t)min((uint64_t)kSegKmers, nk - t0);
-            uint32_t c_unit = 0;
-            for (uint32_t tb = 0; tb < cnt; tb += 64) {
-                bool in = false, again = false;
-                if (tb + lane < cnt) {
-                    Kmer c;
-                    kmer_at<KT, kKmerBio>(rv, o0, len, (t0 + tb + lane) * step, k, c);
-                    const uint32_t res = bloom_member<KT, KB, SPLIT>(c, k, bv);
-                    in = res & 1u;
-                    again = (res & 2u) != 0;
-                }
-                c_unit += (uint32_t)__popcll(__ballot(in));
-                if (bv.rows_read) {
-                    const uint32_t K = KB ? KB : bv.K;
-                    const uint32_t first = SPLIT == 0 || (uint32_t)SPLIT >= K ? K : (uint32_t)SPLIT;
-                    rows_total += (uint64_t)__popcll(__ballot(tb + lane < cnt)) * first +
-                                  (uint64_t)__popcll(__ballot(again)) * (K - first);
-                }
-            }
-            kmer_total += cnt;
-            hit_total += c_unit;
-            if (hits && lane == 0) {
-                if (nk <= kSegKmers) hits[r] = c_unit;
-                else if (c_unit) atomicAdd(&hits[r], c_unit);
-            }
-        }
-    }
-    if (bv.rows_read && lane == 0 && rows_total)
-        atomicAdd(reinterpret_cast<unsigned long long*>(bv.rows_read), (unsigned long long)rows_total);
-    if (partials) {
-        if (lane == 0) { s_hits[wid] = hit_total; s_kmers[wid] = kmer_total; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t a = 0, b = 0;
-            for (int w = 0; w < wpb; ++w) { a += s_hits[w]; b += s_kmers[w]; }
-            partials[blockIdx.x * 2ull] = a;
-            partials[blockIdx.x * 2ull + 1] = b;
-        }
-    }
-}
-
 // ------------------------------------------------------------------ builders
 // Sets bit (doc - group start) of the h rows of every k-mer (step 1) of every
 // record: cobs classic_construct_list / compact_construct_list restated.
@@ -163,40 +64,24 @@ template <int KT, int HT>
 __global__ void __launch_bounds__(kProbeThreads) build_cobs_kernel(ReadView rv,
                                                                    const uint32_t* __restrict__ rec_doc,
                                                                    CobsView bv, uint32_t* rows) {
+    constexpr int NH = HT ? HT : (int)kMaxHashes;
     const int lane = threadIdx.x & 63;
     const uint32_t k = KT ? KT : rv.k;
     const uint32_t h = HT ? HT : bv.h;
-    const uint64_t U = rv.queue[0];
-    for (;;) {
-        const uint64_t base = grab_units(rv.queue, lane, rv.grab);
-        if (base >= U) break;
-        const uint64_t uend = min(base + rv.grab, U);
-        for (uint64_t u = base; u < uend; ++u) {
-            const uint32_t r = rv.unit_read[u];
-            const uint64_t seg = u - rv.unit_ofs[r];
-            const uint64_t o0 = rv.offs[r];
-            const uint64_t len = rv.offs[r + 1] - o0;
-            const uint64_t nk = num_kmers(len, k, 1);
-            const uint64_t t0 = seg * kSegKmers;
-            const uint32_t cnt = (uint32_t)min((uint64_t)kSegKmers, nk - t0);
-            const uint64_t doc = rec_doc[r];
-            if (doc >= bv.D) continue;
-            const uint64_t g = doc / (8 * bv.page), bit = doc % (8 * bv.page);
-            const GroupDesc gd = bv.groups[g];
-            for (uint32_t tb = 0; tb < cnt; tb += 64) {
-                if (tb + lane >= cnt) continue;
-                Kmer c;
-                kmer_at<KT, kKmerCobs>(rv, o0, len, t0 + tb + lane, k, c);
-                Xxh64Pre pre;
-                xxh64_pre<KT>(c, k, pre);
-                for (uint32_t j = 0; j < h; ++j) {
-                    const uint64_t row = fastmod(xxh64_seed<KT>(c, pre, k, j), gd.sig, gd.magic);
-                    const uint64_t byte = gd.base + row * bv.pitch + (bit >> 3);
-                    atomicOr(&rows[byte >> 2], 1u << (bit & 31));
-                }
-            }
+    walk_units(rv, lane, k, 1, [&](const Unit& n) {
+        const uint64_t doc = rec_doc[n.r];
+        if (doc >= bv.D) return;
+        const uint64_t g = doc / (8 * bv.page), bit = doc % (8 * bv.page);
+        const GroupDesc gd = bv.groups[g];
+        for (uint32_t tb = 0; tb < n.cnt; tb += 64) {
+            if (tb + lane >= n.cnt) continue;
+            cobs_hashes<KT, NH>(rv, n, n.t0 + tb + lane, k, h, [&](int, uint64_t hv) {
+                const uint64_t row = fastmod(hv, gd.sig, gd.magic);
+                const uint64_t byte = gd.base + row * bv.pitch + (bit >> 3);
+                atomicOr(&rows[byte >> 2], 1u << (bit & 31));
+            });
         }
-    }
+    });
 }
 
 template <int KT>
@@ -204,32 +89,19 @@ __global__ void __launch_bounds__(kProbeThreads) build_bloom_kernel(ReadView rv,
                                                                     uint32_t* bits) {
     const int lane = threadIdx.x & 63;
     const uint32_t k = KT ? KT : rv.k;
-    const uint64_t U = rv.queue[0];
-    for (;;) {
-        const uint64_t base = grab_units(rv.queue, lane, rv.grab);
-        if (base >= U) break;
-        const uint64_t uend = min(base + rv.grab, U);
-        for (uint64_t u = base; u < uend; ++u) {
-            const uint32_t r = rv.unit_read[u];
-            const uint64_t seg = u - rv.unit_ofs[r];
-            const uint64_t o0 = rv.offs[r];
-            const uint64_t len = rv.offs[r + 1] - o0;
-            const uint64_t nk = num_kmers(len, k, 1);
-            const uint64_t t0 = seg * kSegKmers;
-            const uint32_t cnt = (uint32_t)min((uint64_t)kSegKmers, nk - t0);
-            for (uint32_t tb = 0; tb < cnt; tb += 64) {
-                if (tb + lane >= cnt) continue;
-                Kmer c;
-                kmer_at<KT, kKmerBio>(rv, o0, len, t0 + tb + lane, k, c);
-                uint64_t sl = xxh3_kmer<KT>(c, k), sh = 0;
-                for (uint32_t j = 0; j < bv.K; ++j) {
-                    lcg_step(sl, sh);
-                    const uint64_t idx = fastmod(sh, bv.mbits, bv.magic);
-                    atomicOr(&bits[idx >> 5], 1u << (idx & 31));
-                }
+    walk_units(rv, lane, k, 1, [&](const Unit& n) {
+        for (uint32_t tb = 0; tb < n.cnt; tb += 64) {
+            if (tb + lane >= n.cnt) continue;
+            Kmer c;
+            kmer_at<KT, kKmerBio>(rv, n.o0, n.len, n.t0 + tb + lane, k, c);
+            uint64_t sl = xxh3_kmer<KT>(c, k), sh = 0;
+            for (uint32_t j = 0; j < bv.K; ++j) {
+                lcg_step(sl, sh);
+                const uint64_t idx = fastmod(sh, bv.mbits, bv.magic);
+                atomicOr(&bits[idx >> 5], 1u << (idx & 31));
             }
         }
-    }
+    });
 }
 
 // ------------------------------------------------------------------ misc
@@ -436,48 +308,31 @@ int probe_blocks(uint64_t D, int* waves_per_block, size_t* lds_bytes) {
     return 0;
 }
 
-// Grid of the probe kernel launch_probe_cobs picks for this bank (partials
-// are sized by it).  Cached per variant; every device of a run is an MI355X.
-// Order: fast (D <= 128), bit-sliced (MLST loci), wide (2..16 chunks), slots, general.
-int probe_grid_cobs(const CobsView& bv, uint32_t k) {
-    if (cobs_fast(bv, k)) return grid_cobs_fast(k);
-    if (vslice_take(bv)) return grid_cobs_vslice(bv, k);
-    if (wide_for(bv)) return grid_cobs_wide(bv, k);
-    if (slots_take(bv)) return grid_cobs_slots(bv, k);
-    return grid_cobs_general(bv);
+// The direct COBS probe families in routing order: a bank goes to the first
+// that takes it: fast (D <= 128), bit-sliced (MLST loci), wide (2..16 chunks),
+// slots, general (takes every bank).  The grid that sizes partials and the
+// launch that fills them come from the same entry.  Grids are cached per
+// kernel; every device of a run is an MI355X.
+static const CobsFamily& (*const kCobsFamilies[])() = {fast_family, vslice_family, wide_family, slots_family,
+                                                       general_family};
+
+static const CobsFamily& cobs_family(const CobsView& bv, uint32_t k) {
+    for (auto family : kCobsFamilies) {
+        const CobsFamily& f = family();
+        if (f.take(bv, k)) return f;
+    }
+    return general_family();  // not reached: the last entry takes every bank
 }
+
+int probe_grid_cobs(const CobsView& bv, uint32_t k) { return cobs_family(bv, k).grid(bv, k); }
 
 hipError_t launch_probe_cobs(const ReadView& rv, const CobsView& bv, uint32_t* hits,
                              uint64_t* partials, int blocks, hipStream_t s, const char** kernel) {
-    if (cobs_fast(bv, rv.k)) return launch_cobs_fast(rv, bv, hits, partials, blocks, s, kernel);
-    if (vslice_take(bv)) return launch_cobs_vslice(rv, bv, hits, partials, blocks, s, kernel);
-    if (wide_for(bv)) return launch_cobs_wide(rv, bv, hits, partials, blocks, s, kernel);
-    if (slots_take(bv)) return launch_cobs_slots(rv, bv, hits, partials, blocks, s, kernel);
-    return launch_cobs_general(rv, bv, hits, partials, blocks, s, kernel);
+    return cobs_family(bv, rv.k).launch(rv, bv, hits, partials, blocks, s, kernel);
 }
 
 void probe_kernel_names(std::string& out) {
-    fast_kernel_names(out);
-    vslice_kernel_names(out);
-    wide_kernel_names(out);
-    slots_kernel_names(out);
-    out += "general\n";
-}
-
-int probe_grid_bloom() {
-    static std::atomic<int> cache{0};
-    return cached_grid(cache, [] { return resident_grid(probe_bloom_kernel<21, 7, kBloomSplit>, kProbeThreads, 0); });
-}
-
-hipError_t launch_probe_bloom(const ReadView& rv, const BloomView& bv, uint32_t* hits,
-                              uint64_t* partials, int blocks, hipStream_t s, const char** kernel) {
-    using BloomFn = void (*)(ReadView, BloomView, uint32_t*, uint64_t*);
-    static const struct { const char* name; BloomFn fn; } kBloomKernels[2] = {
-        {"bloom<21,7>", probe_bloom_kernel<21, 7, kBloomSplit>}, {"bloom<0,0>", probe_bloom_kernel<0, 0, kBloomSplit>}};
-    const auto& e = kBloomKernels[rv.k == 21 && bv.K == 7 ? 0 : 1];
-    if (kernel) *kernel = e.name;
-    e.fn<<<blocks, kProbeThreads, 0, s>>>(rv, bv, hits, partials);
-    return hipGetLastError();
+    for (auto family : kCobsFamilies) family().names(out);
 }
 
 hipError_t launch_reduce_partials(const uint64_t* partials, int blocks, uint64_t cols,

@@ -28,6 +28,7 @@
 // cases run through this path and the direct one).  The pieces shared with the
 // COBS probe (a bucket block's reads, the lookup's groups, the plan's common
 // sizes) are in xs_part.h.
+#include "xs_direct.h"
 #include "xs_part.h"
 
 namespace xs {
@@ -241,12 +242,8 @@ __global__ void __launch_bounds__(256) bloom_count_kernel(ReadView rv, const uin
     uint64_t hit_total = 0, kmer_total = 0;
     for (uint64_t u = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; u < U;
          u += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t r = rv.unit_read[u];
-        const uint64_t seg = u - rv.unit_ofs[r];
-        const uint64_t nk = num_kmers(rv.offs[r + 1] - rv.offs[r], k, rv.step);
-        const uint64_t t0 = seg * kSegKmers;
-        const uint32_t cnt = (uint32_t)min((uint64_t)kSegKmers, nk - t0);
-        const uint64_t g = kofs[r] + t0, ge = g + cnt;
+        const Unit n = unit_at(rv, u, k, rv.step);
+        const uint64_t g = kofs[n.r] + n.t0, ge = g + n.cnt;
         uint32_t missed = 0;
         for (uint64_t q = g; q < ge;) {
             const uint32_t bit = (uint32_t)(q & 31);
@@ -255,13 +252,10 @@ __global__ void __launch_bounds__(256) bloom_count_kernel(ReadView rv, const uin
             missed += (uint32_t)__popc(take == 32 ? w : (w & ((1u << take) - 1u)));
             q += take;
         }
-        const uint32_t c = cnt - missed;
-        if (hits) {
-            if (nk <= kSegKmers) hits[r] = c;
-            else if (c) atomicAdd(&hits[r], c);
-        }
+        const uint32_t c = n.cnt - missed;
+        if (hits) store_hit(hits, n.r, c, n.whole());
         hit_total += c;
-        kmer_total += cnt;
+        kmer_total += n.cnt;
     }
     // wave sums, then block sums
     for (int d = 32; d; d >>= 1) {

@@ -1,5 +1,5 @@
 // xs_probe_fast.hip — COBS probe of classic banks of <= 128 docs (one 16-byte row per hash).
-#include "xs_device.h"
+#include "xs_direct.h"
 
 namespace xs {
 
@@ -31,31 +31,24 @@ __global__ void __launch_bounds__(kProbeThreads, 2) probe_cobs_fast(ReadView rv,
     const uint64_t U = rv.queue[0];
     uint64_t kmer_total = 0;
 
+    // Own copy of the queue walk, the store rule and the partials: shared, they change the
+    // register allocation, and the bench leg of fast<21,7> then ran past the parent's slowest run
+    // (profiles/direct_shared_refactor.txt).
     for (;;) {
         const uint64_t base = grab_units(rv.queue, lane, rv.grab);
         if (base >= U) break;
         const uint64_t uend = min(base + rv.grab, U);
         for (uint64_t u = base; u < uend; ++u) {
-            const uint32_t r = rv.unit_read[u];
-            const uint64_t seg = u - rv.unit_ofs[r];
-            const uint64_t o0 = rv.offs[r];
-            const uint64_t len = rv.offs[r + 1] - o0;
-            const uint64_t nk = num_kmers(len, k, step);
-            const uint64_t t0 = seg * kSegKmers;
-            const uint32_t cnt = (uint32_t)min((uint64_t)kSegKmers, nk - t0);
-            kmer_total += cnt;
+            const Unit n = unit_at(rv, u, k, step);
+            kmer_total += n.cnt;
             uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-            for (uint32_t tb = 0; tb < cnt; tb += 64) {
+            for (uint32_t tb = 0; tb < n.cnt; tb += 64) {
                 uint4 m = make_uint4(0u, 0u, 0u, 0u);
-                if (tb + lane < cnt) {
-                    Kmer c;
-                    kmer_at<KT, kKmerCobs>(rv, o0, len, (t0 + tb + lane) * step, k, c);
-                    Xxh64Pre pre;
-                    xxh64_pre<KT>(c, k, pre);
+                if (tb + lane < n.cnt) {
                     uint32_t off[HT];
-#pragma unroll
-                    for (int j = 0; j < HT; ++j)
-                        off[j] = fastmod_small(xxh64_seed<KT>(c, pre, k, (uint64_t)j), (uint32_t)fb.sig, fb.magic) * 16u;
+                    cobs_hashes<KT, HT>(rv, n, (n.t0 + tb + lane) * step, k, HT, [&](int j, uint64_t hv) {
+                        off[j] = fastmod_small(hv, (uint32_t)fb.sig, fb.magic) * 16u;
+                    });
                     m = make_uint4(~0u, ~0u, ~0u, ~0u);
 #pragma unroll
                     for (int j = 0; j < HT; ++j)
@@ -67,7 +60,7 @@ __global__ void __launch_bounds__(kProbeThreads, 2) probe_cobs_fast(ReadView rv,
                 if (nwords > 3) a3 += column_popc32(m.w, X);
             }
             // lane c < 32 holds doc 32q + c of word q after folding the halves
-            const bool whole = nk <= kSegKmers;
+            const bool whole = n.whole();
             const uint32_t acc[4] = {a0, a1, a2, a3};
 #pragma unroll
             for (uint32_t q = 0; q < 4; ++q) {
@@ -77,8 +70,8 @@ __global__ void __launch_bounds__(kProbeThreads, 2) probe_cobs_fast(ReadView rv,
                 if (lane < 32 && d < D) {
                     s_tot[wid][d] += v;
                     if (hits) {
-                        if (whole) hits[(uint64_t)r * D + d] = v;
-                        else if (v) atomicAdd(&hits[(uint64_t)r * D + d], v);
+                        if (whole) hits[(uint64_t)n.r * D + d] = v;
+                        else if (v) atomicAdd(&hits[(uint64_t)n.r * D + d], v);
                     }
                 }
             }
@@ -105,7 +98,7 @@ __global__ void __launch_bounds__(kProbeThreads, 2) probe_cobs_fast(ReadView rv,
 // ------------------------------------------------------------------ launch
 // The fast kernel covers classic banks of <= 128 docs whose image fits 32-bit
 // row offsets, for the (k, h) pairs XspecT trains (species 21/7, MLST 31/1).
-bool cobs_fast(const CobsView& bv, uint32_t k) {
+static bool fast_take(const CobsView& bv, uint32_t k) {
     return bv.G == 1 && bv.nchunks == 1 && bv.D <= 128 && bv.sig0 <= (1ull << 28) &&
            ((k == 21 && bv.h == 7) || (k == 31 && bv.h == 1));
 }
@@ -118,15 +111,12 @@ static const ProbeKernel<FastFn> kFastKernels[2] = {{"fast<21,7>", probe_cobs_fa
 
 static const ProbeKernel<FastFn>& pick_fast(uint32_t k) { return kFastKernels[k == 21 ? 0 : 1]; }
 
-void fast_kernel_names(std::string& out) { table_names(kFastKernels, out); }
+static void fast_names(std::string& out) { table_names(kFastKernels, out); }
 
-int grid_cobs_fast(uint32_t k) {
-    static std::atomic<int> grid[2];
-    return cached_grid(grid[k == 21 ? 0 : 1], [&] { return resident_grid(pick_fast(k).fn, kProbeThreads, 0); });
-}
+static int fast_grid(const CobsView&, uint32_t k) { return pick_fast(k).grid(kProbeThreads, 0); }
 
-hipError_t launch_cobs_fast(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                            int blocks, hipStream_t s, const char** kernel) {
+static hipError_t fast_launch(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
+                              int blocks, hipStream_t s, const char** kernel) {
     FastBank fb;
     fb.rows = bv.rows;
     fb.sig = bv.sig0;
@@ -137,6 +127,11 @@ hipError_t launch_cobs_fast(const ReadView& rv, const CobsView& bv, uint32_t* hi
     if (kernel) *kernel = e.name;
     e.fn<<<blocks, kProbeThreads, 0, s>>>(rv, fb, hits, partials);
     return hipGetLastError();
+}
+
+const CobsFamily& fast_family() {
+    static const CobsFamily f = {fast_take, fast_grid, fast_launch, fast_names};
+    return f;
 }
 
 }  // namespace xs

@@ -1,5 +1,5 @@
 // xs_probe_slots.hip — COBS probe with a compile-time group x chunk row layout (MLST loci, compact banks).
-#include "xs_device.h"
+#include "xs_direct.h"
 
 namespace xs {
 
@@ -38,31 +38,28 @@ __global__ void __launch_bounds__(kProbeThreads, 2) probe_cobs_slots(ReadView rv
     const uint64_t U = rv.queue[0];
     uint64_t kmer_total = 0;
 
+    // Own copy of the queue walk, the hash sequence, the store rule and the partials: with them
+    // shared slots<0,0,1,4> lost a wave per SIMD or ran 1.4 % slower
+    // (profiles/direct_shared_refactor.txt).
     for (;;) {
         const uint64_t base = grab_units(rv.queue, lane, rv.grab);
         if (base >= U) break;
         const uint64_t uend = min(base + rv.grab, U);
         for (uint64_t u = base; u < uend; ++u) {
-            const uint32_t r = rv.unit_read[u];
-            const uint64_t seg = u - rv.unit_ofs[r];
-            const uint64_t o0 = rv.offs[r];
-            const uint64_t len = rv.offs[r + 1] - o0;
-            const uint64_t nk = num_kmers(len, k, step);
-            const uint64_t t0 = seg * kSegKmers;
-            const uint32_t cnt = (uint32_t)min((uint64_t)kSegKmers, nk - t0);
-            kmer_total += cnt;
+            const Unit n = unit_at(rv, u, k, step);
+            kmer_total += n.cnt;
             uint32_t acc[2 * NS];
 #pragma unroll
             for (int i = 0; i < 2 * NS; ++i) acc[i] = 0;
 
-            for (uint32_t tb = 0; tb < cnt; tb += 64) {
-                const bool act = tb + lane < cnt;
+            for (uint32_t tb = 0; tb < n.cnt; tb += 64) {
+                const bool act = tb + lane < n.cnt;
                 uint64_t hv[NH];
 #pragma unroll
                 for (int j = 0; j < NH; ++j) hv[j] = 0;
                 if (act) {
                     Kmer c;
-                    kmer_at<KT, kKmerCobs>(rv, o0, len, (t0 + tb + lane) * step, k, c);
+                    kmer_at<KT, kKmerCobs>(rv, n.o0, n.len, (n.t0 + tb + lane) * step, k, c);
                     Xxh64Pre pre;
                     xxh64_pre<KT>(c, k, pre);
 #pragma unroll
@@ -114,7 +111,7 @@ __global__ void __launch_bounds__(kProbeThreads, 2) probe_cobs_slots(ReadView rv
                 }
             }
             // lane c < 32 holds doc 32q + c of chunk (g, cc) after folding the halves
-            const bool whole = nk <= kSegKmers;
+            const bool whole = n.whole();
 #pragma unroll
             for (int g = 0; g < GM; ++g) {
                 if ((uint32_t)g >= G) continue;
@@ -132,8 +129,8 @@ __global__ void __launch_bounds__(kProbeThreads, 2) probe_cobs_slots(ReadView rv
                         if (lane < 32 && d < glim) {
                             if (v) atomicAdd(reinterpret_cast<unsigned long long*>(&s_tot[d]), (unsigned long long)v);
                             if (hits) {
-                                if (whole) hits[(uint64_t)r * D + d] = v;
-                                else if (v) atomicAdd(&hits[(uint64_t)r * D + d], v);
+                                if (whole) hits[(uint64_t)n.r * D + d] = v;
+                                else if (v) atomicAdd(&hits[(uint64_t)n.r * D + d], v);
                             }
                         }
                     }
@@ -213,20 +210,18 @@ static const ProbeKernel<SlotsFn>& pick_slots(uint32_t k, uint32_t h, SlotShape 
     return kSlotsKernels[v * kSlotShapes + shape_index(s)];
 }
 
-void slots_kernel_names(std::string& out) { table_names(kSlotsKernels, out); }
+static void slots_names(std::string& out) { table_names(kSlotsKernels, out); }
 
-bool slots_take(const CobsView& bv) { return slots_for(bv).gm != 0; }
+static bool slots_take(const CobsView& bv, uint32_t) { return slots_for(bv).gm != 0; }
 
-int grid_cobs_slots(const CobsView& bv, uint32_t k) {
-    static std::atomic<int> slots[3][kSlotShapes];
-    const SlotShape sh = slots_for(bv);
-    // LDS is 16 KB at most: residency is set by registers, not by D
-    return cached_grid(slots[kh_variant(k, bv.h)][shape_index(sh)],
-                       [&] { return resident_grid(pick_slots(k, bv.h, sh).fn, kProbeThreads, 16384); });
+// The occupancy query is made with 16 KB of LDS, the most a slot shape needs,
+// whatever the bank's D: residency is set by registers, not by D.
+static int slots_grid(const CobsView& bv, uint32_t k) {
+    return pick_slots(k, bv.h, slots_for(bv)).grid(kProbeThreads, 16384);
 }
 
-hipError_t launch_cobs_slots(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                             int blocks, hipStream_t s, const char** kernel) {
+static hipError_t slots_launch(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
+                               int blocks, hipStream_t s, const char** kernel) {
     const size_t lds = slots_lds(bv);
     const SlotShape sh = slots_for(bv);
     if (sh.gm == 0) return hipErrorInvalidValue;  // not a slot shape (slots_take is false)
@@ -234,6 +229,11 @@ hipError_t launch_cobs_slots(const ReadView& rv, const CobsView& bv, uint32_t* h
     if (kernel) *kernel = e.name;
     e.fn<<<blocks, kProbeThreads, lds, s>>>(rv, bv, hits, partials, (uint32_t)(lds / sizeof(uint64_t)));
     return hipGetLastError();
+}
+
+const CobsFamily& slots_family() {
+    static const CobsFamily f = {slots_take, slots_grid, slots_launch, slots_names};
+    return f;
 }
 
 }  // namespace xs

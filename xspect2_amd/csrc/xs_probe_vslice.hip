@@ -1,6 +1,6 @@
 // xs_probe_vslice.hip — COBS probe of banks of 1-4 groups of 64-byte pages with one hash
 // (MLST loci of up to 2048 alleles), counting with bit-sliced adders.
-#include "xs_device.h"
+#include "xs_direct.h"
 
 namespace xs {
 
@@ -132,29 +132,26 @@ __global__ void __launch_bounds__(kProbeThreads, kVsMinBlocks) probe_cobs_vslice
     const uint64_t U = rv.queue[0];
     uint64_t kmer_total = 0;
 
+    // Own copy of the queue walk, the hash sequence and the partials: cobs_hashes alone moves
+    // vslice<0,1>'s scratch, and with all pieces shared the MLST leg was 0.5 % slower
+    // (profiles/direct_shared_refactor.txt).
     for (;;) {
         const uint64_t base = grab_units(rv.queue, lane, rv.grab);
         if (base >= U) break;
         const uint64_t uend = min(base + rv.grab, U);
         for (uint64_t u = base; u < uend; ++u) {
-            const uint32_t r = rv.unit_read[u];
-            const uint64_t seg = u - rv.unit_ofs[r];
-            const uint64_t o0 = rv.offs[r];
-            const uint64_t len = rv.offs[r + 1] - o0;
-            const uint64_t nk = num_kmers(len, k, step);
-            const uint64_t t0 = seg * kSegKmers;
-            const uint32_t cnt = (uint32_t)min((uint64_t)kSegKmers, nk - t0);
-            kmer_total += cnt;
+            const Unit n = unit_at(rv, u, k, step);
+            kmer_total += n.cnt;
             uint32_t ones = 0, twos = 0, fours = 0, eights = 0;
             uint32_t p16 = 0, p32 = 0, p64 = 0, p128 = 0, p256 = 0;
-            for (uint32_t tb = 0; tb < cnt; tb += 64) {
-                const uint32_t tile = min(64u, cnt - tb);
+            for (uint32_t tb = 0; tb < n.cnt; tb += 64) {
+                const uint32_t tile = min(64u, n.cnt - tb);
                 uint32_t ri[GM];
 #pragma unroll
                 for (int g = 0; g < GM; ++g) ri[g] = 0;  // past the tile: row 0, loaded and dropped
                 if ((uint32_t)lane < tile) {
                     Kmer c;
-                    kmer_at<KT, kKmerCobs>(rv, o0, len, (t0 + tb + lane) * step, k, c);
+                    kmer_at<KT, kKmerCobs>(rv, n.o0, n.len, (n.t0 + tb + lane) * step, k, c);
                     Xxh64Pre pre;
                     xxh64_pre<KT>(c, k, pre);
                     const uint64_t hv = xxh64_seed<KT>(c, pre, k, 0);
@@ -200,18 +197,15 @@ __global__ void __launch_bounds__(kProbeThreads, kVsMinBlocks) probe_cobs_vslice
             dst[1] = make_uint4(b[4], b[5], b[6], b[7]);
             if (any256) s_p256[wid][lane] = p256;
             __builtin_amdgcn_wave_barrier();
-            const bool whole = nk <= kSegKmers;
-            uint32_t* hrow = hits ? hits + (uint64_t)r * D : nullptr;
+            const bool whole = n.whole();
+            uint32_t* hrow = hits ? hits + (uint64_t)n.r * D : nullptr;
             for (uint32_t d = (uint32_t)lane; d < D; d += 64) {
                 uint32_t v = s_cnt[d];
 #pragma unroll
                 for (int sl = 1; sl < S; ++sl) v += s_cnt[sl * kDocs + d];
                 if (any256) v += ((s_p256[wid][d >> 5] >> (d & 31)) & 1u) << 8;
                 if (v) atomicAdd(reinterpret_cast<unsigned long long*>(&s_tot[d]), (unsigned long long)v);
-                if (hrow) {
-                    if (whole) hrow[d] = v;
-                    else if (v) atomicAdd(&hrow[d], v);
-                }
+                if (hrow) store_hit(hrow, d, v, whole);
             }
         }
     }
@@ -234,7 +228,7 @@ __global__ void __launch_bounds__(kProbeThreads, kVsMinBlocks) probe_cobs_vslice
 // bank kind is not asked: a classic bank (or doc slice) of 505-512 docs with
 // one hash has a 64-byte page too and is taken
 // (tests/test_gpu_probe_kernels.py pins both).
-bool vslice_take(const CobsView& bv) {
+static bool vslice_take(const CobsView& bv, uint32_t) {
     return bv.G >= 1 && bv.G <= 4 && bv.h == 1 && bv.page == 64 && bv.pitch == 64 && bv.D <= bv.G * 512ull &&
            bv.sig_max < (1ull << 30) && (uint64_t)bv.G * bv.sig_max * 64 < (1ull << 32);
 }
@@ -252,20 +246,21 @@ static const ProbeKernel<VsFn>& pick_vslice(uint32_t k, uint32_t G) {
     return kVsliceKernels[(k == 31 ? 0 : 4) + (G - 1)];  // G = 1..4 (vslice_take)
 }
 
-void vslice_kernel_names(std::string& out) { table_names(kVsliceKernels, out); }
+static void vslice_names(std::string& out) { table_names(kVsliceKernels, out); }
 
-int grid_cobs_vslice(const CobsView& bv, uint32_t k) {
-    static std::atomic<int> grid[2][4];  // k == 31 x G
-    return cached_grid(grid[k == 31 ? 0 : 1][bv.G - 1],
-                       [&] { return resident_grid(pick_vslice(k, bv.G).fn, kProbeThreads, 0); });
-}
+static int vslice_grid(const CobsView& bv, uint32_t k) { return pick_vslice(k, bv.G).grid(kProbeThreads, 0); }
 
-hipError_t launch_cobs_vslice(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                              int blocks, hipStream_t s, const char** kernel) {
+static hipError_t vslice_launch(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
+                                int blocks, hipStream_t s, const char** kernel) {
     const ProbeKernel<VsFn>& e = pick_vslice(rv.k, bv.G);
     if (kernel) *kernel = e.name;
     e.fn<<<blocks, kProbeThreads, 0, s>>>(rv, bv, hits, partials);
     return hipGetLastError();
+}
+
+const CobsFamily& vslice_family() {
+    static const CobsFamily f = {vslice_take, vslice_grid, vslice_launch, vslice_names};
+    return f;
 }
 
 }  // namespace xs

@@ -1,6 +1,6 @@
 // xs_probe_wide.hip — COBS probe with C chunk lanes per k-mer: classic banks of 129..2048 docs,
 // compact banks of 2..4 groups of 2..4-chunk pages (MLST loci).
-#include "xs_device.h"
+#include "xs_direct.h"
 
 namespace xs {
 
@@ -58,19 +58,16 @@ __global__ void __launch_bounds__(kProbeThreads, kWideMinBlocks) probe_cobs_wide
     const uint64_t U = rv.queue[0];
     uint64_t kmer_total = 0;
 
+    // Own copy of the queue walk, the hash sequence, the store rule and the partials: each of
+    // them, alone, costs a wide<0,0,...> kernel scratch or a wave per SIMD
+    // (profiles/direct_shared_refactor.txt).
     for (;;) {
         const uint64_t base = grab_units(rv.queue, lane, rv.grab);
         if (base >= U) break;
         const uint64_t uend = min(base + rv.grab, U);
         for (uint64_t u = base; u < uend; ++u) {
-            const uint32_t r = rv.unit_read[u];
-            const uint64_t seg = u - rv.unit_ofs[r];
-            const uint64_t o0 = rv.offs[r];
-            const uint64_t len = rv.offs[r + 1] - o0;
-            const uint64_t nk = num_kmers(len, k, step);
-            const uint64_t t0 = seg * kSegKmers;
-            const uint32_t cnt = (uint32_t)min((uint64_t)kSegKmers, nk - t0);
-            kmer_total += cnt;
+            const Unit n = unit_at(rv, u, k, step);
+            kmer_total += n.cnt;
             // group g, chunk cc, words q: 16-bit counters, reg [g][2*cc + (q >> 1)]
             uint32_t acc[GM][2 * C];
 #pragma unroll
@@ -78,8 +75,8 @@ __global__ void __launch_bounds__(kProbeThreads, kWideMinBlocks) probe_cobs_wide
 #pragma unroll
                 for (int i = 0; i < 2 * C; ++i) acc[g][i] = 0;
 
-            for (uint32_t tb = 0; tb < cnt; tb += 64) {
-                const bool act = tb + lane < cnt;
+            for (uint32_t tb = 0; tb < n.cnt; tb += 64) {
+                const bool act = tb + lane < n.cnt;
                 uint32_t ri[GM][NH];  // row index of hash j in group g
 #pragma unroll
                 for (int g = 0; g < GM; ++g)
@@ -87,7 +84,7 @@ __global__ void __launch_bounds__(kProbeThreads, kWideMinBlocks) probe_cobs_wide
                     for (int j = 0; j < NH; ++j) ri[g][j] = 0;
                 if (act) {
                     Kmer c;
-                    kmer_at<KT, kKmerCobs>(rv, o0, len, (t0 + tb + lane) * step, k, c);
+                    kmer_at<KT, kKmerCobs>(rv, n.o0, n.len, (n.t0 + tb + lane) * step, k, c);
                     Xxh64Pre pre;
                     xxh64_pre<KT>(c, k, pre);
 #pragma unroll
@@ -98,7 +95,7 @@ __global__ void __launch_bounds__(kProbeThreads, kWideMinBlocks) probe_cobs_wide
                             for (int g = 0; g < GM; ++g) ri[g][j] = fastmod_small(hv, (uint32_t)gd[g].sig, gd[g].magic);
                         }
                 }
-                const uint32_t tile = min(64u, cnt - tb);
+                const uint32_t tile = min(64u, n.cnt - tb);
 #pragma unroll
                 for (int s0 = 0; s0 < C; s0 += P) {
                     if ((uint32_t)(s0 * K) >= tile) continue;  // uniform
@@ -151,7 +148,7 @@ __global__ void __launch_bounds__(kProbeThreads, kWideMinBlocks) probe_cobs_wide
                 }
             }
             // lane t < 32 holds doc g * gdocs + 128 cc + 32 q + t after folding the halves
-            const bool whole = nk <= kSegKmers;
+            const bool whole = n.whole();
 #pragma unroll
             for (int g = 0; g < GM; ++g) {
 #pragma unroll
@@ -167,8 +164,8 @@ __global__ void __launch_bounds__(kProbeThreads, kWideMinBlocks) probe_cobs_wide
                         if (lane < 32 && l0 + lane < gdocs && d < D) {
                             if (v) atomicAdd(reinterpret_cast<unsigned long long*>(&s_tot[d]), (unsigned long long)v);
                             if (hits) {
-                                if (whole) hits[(uint64_t)r * D + d] = v;
-                                else if (v) atomicAdd(&hits[(uint64_t)r * D + d], v);
+                                if (whole) hits[(uint64_t)n.r * D + d] = v;
+                                else if (v) atomicAdd(&hits[(uint64_t)n.r * D + d], v);
                             }
                         }
                     }
@@ -194,7 +191,7 @@ __global__ void __launch_bounds__(kProbeThreads, kWideMinBlocks) probe_cobs_wide
 // Wide kernel chunk lanes for a bank (0: not taken): classic banks of 2..16
 // data chunks; compact banks of 2..4 groups whose pages are 2..4 chunks (MLST
 // loci: 3 groups of 64-byte pages).
-int wide_for(const CobsView& bv) {
+static int wide_for(const CobsView& bv) {
     if (bv.G < 1 || bv.G > 4 || bv.nchunks < 2 || bv.sig_max >= (1ull << 30)) return 0;  // fastmod_small
     if (bv.G == 1 && bv.nchunks > 16) return 0;
     if (bv.G > 1 && bv.nchunks > 4) return 0;
@@ -231,31 +228,36 @@ static const ProbeKernel<WideFn> kWideKernels[3 * 4 * 4] = {
 
 static int wide_c_index(int c) { return c == 2 ? 0 : c == 4 ? 1 : c == 8 ? 2 : 3; }
 
-// c = wide_for(bv) (non-zero), G = 1..4
-static const ProbeKernel<WideFn>& pick_wide(uint32_t k, uint32_t h, int c, uint32_t G) {
-    int v = kh_variant(k, h);
-    if (v == 0 && G > 1) v = 2;  // species (k, h) on a compact bank: the general-(k, h) kernel
-    return kWideKernels[(v * 4 + (int)(G - 1)) * 4 + wide_c_index(c)];
+static bool wide_take(const CobsView& bv, uint32_t) { return wide_for(bv) != 0; }
+
+// The kernel of a bank that wide_take accepts (G = 1..4).
+static const ProbeKernel<WideFn>& pick_wide(const CobsView& bv, uint32_t k) {
+    int v = kh_variant(k, bv.h);
+    if (v == 0 && bv.G > 1) v = 2;  // species (k, h) on a compact bank: the general-(k, h) kernel
+    return kWideKernels[(v * 4 + (int)(bv.G - 1)) * 4 + wide_c_index(wide_for(bv))];
 }
 
-void wide_kernel_names(std::string& out) { table_names(kWideKernels, out); }
+static void wide_names(std::string& out) { table_names(kWideKernels, out); }
 
-int grid_cobs_wide(const CobsView& bv, uint32_t k) {
-    static std::atomic<int> wide[3][4][4];  // (k, h) variant x G x C
-    const int c = wide_for(bv);
-    return cached_grid(wide[kh_variant(k, bv.h)][bv.G - 1][wide_c_index(c)], [&] {
-        return resident_grid(pick_wide(k, bv.h, c, bv.G).fn, kProbeThreads, slots_lds(bv) > 8192 ? 16384 : 8192);
-    });
+// The occupancy query is made with 8 or 16 KB of LDS, whichever the first
+// bank that reaches a kernel needs, and its answer kept for every later bank.
+static int wide_grid(const CobsView& bv, uint32_t k) {
+    return pick_wide(bv, k).grid(kProbeThreads, slots_lds(bv) > 8192 ? 16384 : 8192);
 }
 
-hipError_t launch_cobs_wide(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
-                            int blocks, hipStream_t s, const char** kernel) {
+static hipError_t wide_launch(const ReadView& rv, const CobsView& bv, uint32_t* hits, uint64_t* partials,
+                              int blocks, hipStream_t s, const char** kernel) {
     const size_t lds = slots_lds(bv);
-    const ProbeKernel<WideFn>& e = pick_wide(rv.k, bv.h, wide_for(bv), bv.G);
+    const ProbeKernel<WideFn>& e = pick_wide(bv, rv.k);
     if (!e.fn) return hipErrorInvalidDeviceFunction;  // a table slot wide_for never selects
     if (kernel) *kernel = e.name;
     e.fn<<<blocks, kProbeThreads, lds, s>>>(rv, bv, hits, partials, (uint32_t)(lds / sizeof(uint64_t)));
     return hipGetLastError();
+}
+
+const CobsFamily& wide_family() {
+    static const CobsFamily f = {wide_take, wide_grid, wide_launch, wide_names};
+    return f;
 }
 
 }  // namespace xs
