@@ -253,6 +253,55 @@ int xs_best_device(const uint32_t* d_hits, uint64_t n, uint64_t num_docs, uint32
 int xs_gather_reads_device(const void* d_seqs, const uint64_t* d_offsets, const uint32_t* d_index, uint64_t m,
                            void* d_out_seqs, const uint64_t* d_out_offsets, void* stream);
 
+/* Read filtering on the device.  The reference decides per read with
+ * round(h / n, 2) >= threshold, or for threshold -1 with "the label's rounded
+ * score is the read's largest" (ModelResult.get_filter_mask and
+ * get_filtered_subsequence_labels, src/xspect/models/result.py:92-149).
+ * round(x, 2) is monotone in the double x = h / n, so 101 cuts reproduce it by
+ * comparison: cut[c] is the smallest double x with round(x, 2) >= c/100 (ties
+ * to even, as Python rounds), and centi(x) = the number of cuts <= x, minus one,
+ * is 100 * round(x, 2).  A threshold t in [0, 1] keeps a read iff centi(x) >=
+ * min{c : c/100 >= t}; -1 keeps it iff centi(h_label / n) == centi(h_max / n).
+ *
+ * The 101 cuts (n must be 101), built on the host in exact arithmetic; no
+ * device is touched. */
+int xs_filter_cuts(double* out, uint64_t n);
+/* The keep decision of result.py:92-149 over a device hit matrix (n x num_docs
+ * uint32, rows unpadded) and the reads' k-mer counts, on `stream`: d_keep[r] =
+ * 1 or 0, d_label_hits[r] (NULL ok) = the label's count.  d_doc_mask (NULL ok):
+ * num_docs bytes on the device, a 0 byte drops that doc from the row's maximum
+ * (predict's exclude_ids).  The kernel reads it for threshold -1 alone, but a
+ * call that passes one, in either mode, first copies the label's byte back and
+ * waits for `stream` once, because a masked label is refused; pass NULL with a
+ * threshold in [0, 1] to avoid that wait.  A read with no k-mers is never
+ * kept.  XS_ERR_ARG: a threshold outside [0, 1] that is not exactly -1 (NaN
+ * included), label_doc >= num_docs, a masked label. */
+int xs_filter_keep_device(const uint32_t* d_hits, const uint64_t* d_num_kmers, uint64_t n, uint64_t num_docs,
+                          uint64_t label_doc, const uint8_t* d_doc_mask, double threshold, uint8_t* d_keep,
+                          uint32_t* d_label_hits, void* stream);
+/* The kept reads of a batch in file order, replacing the id list and the
+ * second parse of file_io.py:166-191 and the hand-off of main.py:116-145:
+ * d_index[0..m) = the reads with a non-zero keep byte, ascending; d_out_offsets
+ * [0..m] = the running sums of their lengths from 0 (what
+ * xs_gather_reads_device takes); d_counts = {m, kept bytes}.  d_offsets: the
+ * reads' n + 1 offsets.  A multi-block exclusive scan: deterministic, and
+ * nothing past d_index[m - 1], d_out_offsets[m] and d_counts[1] is written.
+ * n < 2^32.  The scan's block sums (16 bytes per 1024 reads) are allocated and
+ * freed in stream order on the calling thread's current device, which must be
+ * the device that owns `stream` and the buffers. */
+int xs_filter_compact_device(const uint8_t* d_keep, const uint64_t* d_offsets, uint64_t n, uint32_t* d_index,
+                             uint64_t* d_out_offsets, uint64_t* d_counts, void* stream);
+/* Probe host reads and keep or drop each (result.py:92-149) without the hit
+ * matrix leaving the device: keep_out[r] = 1 or 0.  label_doc: the label's doc
+ * index (0 for an rbloom bank); doc_mask: num_docs bytes on the host or NULL;
+ * threshold and errors as xs_filter_keep_device.  label_hits_out,
+ * num_kmers_out and totals_out (D+1 entries, as xs_query_best) may be NULL.
+ * No output needs initialising; every element of every given output is
+ * written; n = 0 writes the totals only. */
+int xs_query_keep(xs_bank* bank, const char* seqs, const uint64_t* offsets, uint64_t n, uint32_t step,
+                  uint64_t label_doc, const uint8_t* doc_mask, double threshold, uint8_t* keep_out,
+                  uint32_t* label_hits_out, uint64_t* num_kmers_out, uint64_t* totals_out);
+
 /* MLST chunk scoring (probabilistic_filter_mlst_model.py:237-256): for chunk
  * hit rows hits[c][d] whose owner is seq_of_chunk[c] (non-decreasing), sum
  * hits[c][d] into scores[seq][d] only where hits[c][d] > threshold

@@ -158,6 +158,10 @@ SIGNATURES = {
     "xs_query_best": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp]),
     "xs_gather_reads_device": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "xs_best_device": (_int, [_vp, _u64, _u64, _vp, _vp, _vp]),
+    "xs_filter_cuts": (_int, [_vp, _u64]),
+    "xs_filter_keep_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, ctypes.c_double, _vp, _vp, _vp]),
+    "xs_filter_compact_device": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "xs_query_keep": (_int, [_vp, _vp, _vp, _u64, _u32, _u64, _vp, ctypes.c_double, _vp, _vp, _vp, _vp]),
     "xs_mlst_sum": (_int, [_vp, _vp, _vp, _u64, _u64, _u32, _vp]),
     "xs_mlst_query": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),
     "xs_mlst_top_device": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp]),

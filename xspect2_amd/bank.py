@@ -404,6 +404,33 @@ class Bank:
                                    _ptr(bh), _ptr(nk), _ptr(tot) if tot is not None else None))
         return best, bh, nk, tot
 
+    def query_keep(self, reads: PackedReads | Iterable, label_doc: int, threshold: float, step: int = 1,
+                   doc_mask: np.ndarray | None = None, want_totals: bool = False, want_counts: bool = True):
+        """xs_query_keep: per read whether its score for doc `label_doc` passes
+        `threshold` (-1: the label's rounded score is the read's largest over the
+        docs `doc_mask` leaves in), decided on the device as the reference's
+        ``get_filter_mask`` decides it.  Returns (keep [n] uint8, label_hits [n]
+        uint32, num_kmers [n] uint64, totals [D + 1] uint64 or None); the hit
+        matrix stays in HBM.  want_counts=False: label_hits and num_kmers are
+        None and only the keep byte of each read crosses PCIe."""
+        pr = reads if isinstance(reads, PackedReads) else pack_sequences(reads)
+        if step < 1:
+            raise ValueError("step must be >= 1")
+        mask = None
+        if doc_mask is not None:
+            mask = np.ascontiguousarray(doc_mask, dtype=np.uint8)
+            if mask.size != self.num_docs:
+                raise ValueError("doc_mask needs one byte per doc")
+        keep = np.empty(pr.n, dtype=np.uint8)
+        lh = np.empty(pr.n, dtype=np.uint32) if want_counts else None
+        nk = np.empty(pr.n, dtype=np.uint64) if want_counts else None
+        tot = np.empty(self.num_docs + 1, dtype=np.uint64) if want_totals else None
+        check(load().xs_query_keep(self.handle, _ptr(pr.buf), _ptr(pr.offsets), pr.n, step, int(label_doc),
+                                   _ptr(mask) if mask is not None else None, float(threshold), _ptr(keep),
+                                   _ptr(lh) if want_counts else None, _ptr(nk) if want_counts else None,
+                                   _ptr(tot) if tot is not None else None))
+        return keep, lh, nk, tot
+
     def query_device(self, seqs, seq_bytes: int, offsets, n: int, step: int = 1, hits=None,
                      num_kmers=None, totals=None, stream: int | None = None) -> None:
         """Enqueue a query on device buffers (torch tensors or raw device pointers)."""
@@ -739,6 +766,39 @@ def mlst_chunk_top_device(hits, n_chunks: int, num_docs: int, owner_begin, n_own
                                           _dptr(top), _dptr(top_score), _dptr(n_tied), out_stride, stream))
 
 
+FILTER_CUTS = 101
+FILTER_COMPACT_BLOCK = 1024  # reads per block of filter_compact_device's scan (kCompactBlock)
+
+
+def filter_cuts() -> np.ndarray:
+    """xs_filter_cuts: cut[c], c = 0 .. 100, the smallest double x with
+    ``round(x, 2) >= c / 100``; ``round(x, 2) * 100`` is the number of cuts <= x,
+    minus one.  Built on the host; no device is touched."""
+    out = np.empty(FILTER_CUTS, dtype=np.float64)
+    check(load().xs_filter_cuts(_ptr(out), out.size))
+    return out
+
+
+def filter_keep_device(hits, num_kmers, n: int, num_docs: int, label_doc: int, threshold: float, keep,
+                       label_hits=None, doc_mask=None, stream: int | None = None) -> None:
+    """xs_filter_keep_device: keep[r] = 1 / 0 for the n rows of a device hit
+    matrix (n x num_docs uint32) and their k-mer counts (uint64), the reference's
+    ``round(h / n, 2) >= threshold`` (or, threshold -1, the label's rounded score
+    is the row's largest); label_hits (optional) takes the label's column;
+    doc_mask (optional, num_docs bytes on the device) drops docs from the maximum."""
+    check(load().xs_filter_keep_device(_dptr(hits), _dptr(num_kmers), n, num_docs, int(label_doc), _dptr(doc_mask),
+                                       float(threshold), _dptr(keep), _dptr(label_hits), stream))
+
+
+def filter_compact_device(keep, offsets, n: int, index, out_offsets, counts, stream: int | None = None) -> None:
+    """xs_filter_compact_device: index[0..m) = the reads with a non-zero keep
+    byte, ascending; out_offsets[0..m] = the running sums of their lengths
+    (``gather_reads_device``'s out_offsets); counts = (m, kept bytes).  Size index
+    for n and out_offsets for n + 1 entries: m is known only afterwards."""
+    check(load().xs_filter_compact_device(_dptr(keep), _dptr(offsets), n, _dptr(index), _dptr(out_offsets),
+                                          _dptr(counts), stream))
+
+
 def gather_reads_device(seqs, offsets, index, m: int, out_seqs, out_offsets, stream: int | None = None) -> None:
     """xs_gather_reads_device: out read j = read index[j] at out_offsets[j]."""
     check(load().xs_gather_reads_device(_dptr(seqs), _dptr(offsets), _dptr(index), m, _dptr(out_seqs),
@@ -761,7 +821,7 @@ def _dptr(x) -> int | None:
     return ptr()
 
 
-__all__ = ["Bank", "bloom_parameters", "cobs_signature_size", "KIND_NAMES", "pinned_empty", "max_kmers", "probe_kernel_names",
+__all__ = ["Bank", "filter_cuts", "filter_keep_device", "filter_compact_device", "bloom_parameters", "cobs_signature_size", "KIND_NAMES", "pinned_empty", "max_kmers", "probe_kernel_names",
            "mlst_top_device", "mlst_type", "mlst_type_contigs", "mlst_type_ranked", "mlst_ranks_device",
            "mlst_chunk_ranks_device", "mlst_split_size", "mlst_split_device",
            "mlst_chunk_top_device", "DeviceReads", "XS_BANK_COBS_CLASSIC", "XS_BANK_COBS_COMPACT", "XS_BANK_RBLOOM", "_lib"]

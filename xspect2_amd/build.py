@@ -25,7 +25,8 @@ SO_PATH = PKG / "libxspect_hip.so"
 SOURCE_NAMES = ["xs_api.cpp", "xs_bank_io.cpp", "xs_bank_header.cpp", "xs_query.cpp", "xs_mlst.cpp", "xs_pool.cpp", "xs_fastx.cpp",
                 "xs_fastx_parse.cpp", "xs_fastx_devside.cpp", "xs_fastx_dev.hip", "xs_json.cpp", "xs_kernels.hip",
                 "xs_probe_fast.hip", "xs_probe_vslice.hip", "xs_probe_wide.hip", "xs_probe_slots.hip", "xs_probe_general.hip",
-                "xs_probe_bloom.hip", "xs_probe_bloompart.hip", "xs_probe_cobspart.hip", "xs_mlst_top.hip", "xs_mlst_chunks.hip", "xs_mlst_ranks.hip"]
+                "xs_probe_bloom.hip", "xs_probe_bloompart.hip", "xs_probe_cobspart.hip", "xs_mlst_top.hip", "xs_mlst_chunks.hip", "xs_mlst_ranks.hip",
+                "xs_filter.cpp", "xs_filter.hip"]
 HEADER_NAMES = ["xs_internal.h", "xs_device.h", "xs_direct.h", "xs_part.h", "xs_host.h", "xs_query.h", "xs_mlst_plan.h", "xs_bank_header.h", "xs_hitsink.h",
                 "xs_fastx.h"]
 SOURCES = [CSRC / s for s in SOURCE_NAMES]

@@ -344,6 +344,39 @@ hipError_t launch_narrow_hits(const uint32_t* src, void* dst, uint64_t n, int hi
 hipError_t launch_gather_reads(const uint8_t* seqs, const uint64_t* offs, const uint32_t* index, uint64_t m,
                                uint8_t* out, const uint64_t* out_offs, hipStream_t s);
 
+// ---- read filtering (xs_filter.cpp, xs_filter.hip) ----------------------------
+// cut[c] = the smallest double x with round(x, 2) >= c/100 in Python's sense (ties to even): round(x, 2)
+// is monotone in x, so comparisons against the cuts give the reference's decision exactly.
+constexpr int kFilterCuts = 101;
+struct FilterCuts {
+    double c[kFilterCuts];
+};
+const FilterCuts& filter_cuts();  // built once on the host, in exact arithmetic
+// 100 * round(x, 2) for x in [0, 1]: the number of cuts <= x, minus one (a guess one off at most, corrected)
+__host__ __device__ inline int filter_centi(double x, const double* cut) {
+    int g = (int)(x * 100.0);
+    g = g < 0 ? 0 : g > 100 ? 100 : g;
+    if (g < 100 && x >= cut[g + 1]) ++g;
+    else if (g > 0 && x < cut[g]) --g;
+    return g;
+}
+// The mode of a filter threshold: c_min = min{c : c/100 >= t} for t in [0, 1], -1 for t == -1 (the
+// label's rounded score is the row's largest); false for any other t (NaN included).
+bool filter_mode(double threshold, int* c_min);
+// keep[r] (0 / 1) and label_hits[r] (may be null) of n hit rows on the host, as launch_filter_keep decides
+void filter_keep_rows(const uint32_t* rows, const uint64_t* nk, uint64_t n, uint64_t D, uint64_t label,
+                      const uint8_t* mask, int c_min, uint8_t* keep, uint32_t* label_hits);
+// The same over a device matrix (rows of D uint32, no padding); mask: D bytes on the device or null, a
+// 0 byte drops the doc from the row's maximum; a read without k-mers is never kept.
+hipError_t launch_filter_keep(const uint32_t* hits, const uint64_t* nk, uint64_t n, uint64_t D, uint64_t label,
+                              const uint8_t* mask, int c_min, uint8_t* keep, uint32_t* label_hits, hipStream_t s);
+// Reads per block of the compaction's scan.
+constexpr int kCompactBlock = 1024;
+// index[0..m) = the kept reads ascending, out_offs[0..m] = the running sums of their lengths from 0,
+// counts = {m, kept bytes}; nothing past index[m - 1] and out_offs[m] is written.  n < 2^32.
+hipError_t launch_filter_compact(const uint8_t* keep, const uint64_t* offs, uint64_t n, uint32_t* index,
+                                 uint64_t* out_offs, uint64_t* counts, hipStream_t s);
+
 // ---- device-mode reader (xs_fastx_dev.hip) ----------------------------------
 // Text bytes per tile of the newline index (a window's device copy is padded
 // with zeros to a whole tile).

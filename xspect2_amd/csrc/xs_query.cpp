@@ -731,6 +731,63 @@ int xs_query_best(xs_bank* b, const char* seqs, const uint64_t* offsets, uint64_
     });
 }
 
+int xs_query_keep(xs_bank* b, const char* seqs, const uint64_t* offsets, uint64_t n, uint32_t step, uint64_t label_doc,
+                  const uint8_t* doc_mask, double threshold, uint8_t* keep_out, uint32_t* label_hits_out,
+                  uint64_t* num_kmers_out, uint64_t* totals_out) {
+    return xs::guard([&]() -> int {
+        if (!b || !offsets || ((!seqs || !keep_out) && n)) return fail(XS_ERR_ARG, "null argument");
+        int c_min = 0;
+        if (!filter_mode(threshold, &c_min)) return fail(XS_ERR_ARG, "threshold must be in [0, 1] or -1");
+        const uint64_t cols = b->cols();
+        if (label_doc >= cols) return fail(XS_ERR_ARG, "label_doc out of range");
+        if (doc_mask && !doc_mask[label_doc]) return fail(XS_ERR_ARG, "label_doc is masked out");
+        std::lock_guard<std::mutex> lk(b->mu);
+        HIPCHK(hipSetDevice(b->device));
+        if (n == 0) {
+            if (totals_out) memset(totals_out, 0, (cols + 1) * 8);
+            return XS_OK;
+        }
+        if (n <= kSmallReads && n * cols <= (1u << 16)) {  // a small request: the decision made on the host
+            std::vector<uint32_t> rows(n * cols);
+            std::vector<uint64_t> nk(n), tot(cols + 1);
+            bool done = false;
+            if (int rc = query_small(b, seqs, offsets, n, step, rows.data(), 4, nk.data(), tot.data(), &done)) return rc;
+            if (done) {
+                filter_keep_rows(rows.data(), nk.data(), n, cols, label_doc, doc_mask, c_min, keep_out, label_hits_out);
+                if (num_kmers_out) memcpy(num_kmers_out, nk.data(), n * 8);
+                if (totals_out) memcpy(totals_out, tot.data(), (cols + 1) * 8);
+                return XS_OK;
+            }
+        }
+        if (int rc = b->hits.ensure(n * cols * 4)) return rc;
+        if (int rc = b->nk.ensure(n * 8)) return rc;
+        if (int rc = b->best.ensure(n * 5)) return rc;  // the label's hits, then the keep bytes
+        uint32_t* d_hits = b->hits.as<uint32_t>();
+        uint32_t* d_lh = b->best.as<uint32_t>();
+        uint8_t* d_keep = reinterpret_cast<uint8_t*>(d_lh + n);
+        uint8_t* d_mask = nullptr;
+        if (doc_mask && c_min < 0) {  // only the row maximum of max mode reads it
+            if (int rc = b->tmp.ensure(cols)) return rc;
+            d_mask = b->tmp.as<uint8_t>();
+        }
+        std::vector<uint64_t> tot(totals_out ? cols + 1 : 0);
+        HostQuery q{seqs, offsets, nullptr, n, step};
+        q.d_hits = d_hits;
+        q.d_nk = b->nk.as<uint64_t>();
+        if (totals_out) q.tot_host = tot.data();
+        if (int rc = query_host(b, q)) return rc;
+        if (d_mask) HIPCHK(hipMemcpyAsync(d_mask, doc_mask, cols, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(launch_filter_keep(d_hits, q.d_nk, n, cols, label_doc, d_mask, c_min, d_keep, d_lh, b->stream));
+        HIPCHK(hipMemcpyAsync(keep_out, d_keep, n, hipMemcpyDeviceToHost, b->stream));
+        if (label_hits_out) HIPCHK(hipMemcpyAsync(label_hits_out, d_lh, n * 4, hipMemcpyDeviceToHost, b->stream));
+        if (num_kmers_out)
+            HIPCHK(hipMemcpyAsync(num_kmers_out, b->nk.p, n * 8, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (totals_out) memcpy(totals_out, tot.data(), (cols + 1) * 8);
+        return XS_OK;
+    });
+}
+
 int xs_query_totals(xs_bank* b, const char* seqs, const uint64_t* offsets, uint64_t n,
                     uint32_t step, uint64_t* totals_out, uint64_t* total_kmers_out) {
     return xs::guard([&]() -> int {

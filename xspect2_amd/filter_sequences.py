@@ -10,14 +10,22 @@ prediction is the columnar one (``predict_columnar``: one batched GPU probe
 per reader window, no per-read dictionaries), the masks are computed over the
 hit matrix (``MatrixResult.get_filter_mask``) and the FASTA is written by the
 native writer in Bio.SeqIO's layout.
+
+Without a classification output nothing needs the hit matrix, and a file takes
+one pass (``_one_pass``): each reader batch is probed and decided on the device
+(``xs_query_keep``), one keep byte per read comes back, and the kept records
+are written from the batch in hand, so the file is parsed once.
 """
 from __future__ import annotations
 
+import os
 from pathlib import Path
 
 import numpy as np
 
 from .file_io import prepare_input_output_paths, read_batches
+from .packing import PackedIds
+from .pipeline import _partial
 
 
 def filter_sequences(input_file: Path, output_file: Path, included_ids: list[str]) -> None:
@@ -38,10 +46,57 @@ def filter_sequences(input_file: Path, output_file: Path, included_ids: list[str
         Path(output_file).write_text("", encoding="utf-8")
 
 
+def _one_pass(model, label: str, threshold: float, step: int, current_path: Path, fasta_out: Path) -> int | None:
+    """One parse of `current_path`: every batch of the host reader is probed and
+    decided on the device (``Bank.query_keep``: one byte per read comes back),
+    and its kept records go from the same batch to ``<fasta_out>.partial``,
+    which takes the output's name once the file is through.  Returns the records
+    written (0: no file), or None where the reference's by-id rule over the
+    whole file may differ and the two-pass path has to produce the files: an
+    empty input, repeated read ids, a read called "misclassified", equal labels,
+    arguments that raise.  The partial file is dropped then, as on an error."""
+    target = model.filter_target(label, threshold)
+    if not isinstance(target, tuple) or model.index is None:
+        return None
+    col, mask = target
+    partial = _partial(fasta_out)
+    ids = []
+    written = 0
+    try:
+        for b in read_batches(current_path, pinned=True):
+            if (b.lengths() <= model.k).any():
+                raise ValueError("Invalid sequence, must be longer than k")
+            keep = model.index.query_keep(b.packed, col, threshold, step, mask, want_counts=False)[0]
+            idx = np.flatnonzero(keep).astype(np.uint32)
+            ids.append(b.ids_packed())
+            if idx.size:
+                b.write_fasta(partial, idx, append=written > 0)
+                written += int(idx.size)
+        all_ids = PackedIds.concat(ids) if ids else []
+        if not len(all_ids) or all_ids.has_duplicates() or "misclassified" in all_ids:
+            partial.unlink(missing_ok=True)
+            return None
+    except BaseException:
+        partial.unlink(missing_ok=True)
+        raise
+    if written:
+        os.replace(partial, fasta_out)
+    return written
+
+
 def _filter(model, label: str, input_path: Path, output_path: Path, threshold: float,
             classification_output_path: Path | None, step: int, what: str) -> None:
     input_paths, get_output_path = prepare_input_output_paths(Path(input_path))
     for idx, current_path in enumerate(input_paths):
+        if not classification_output_path:
+            filter_output_path = get_output_path(idx, Path(output_path))
+            written = _one_pass(model, label, threshold, step, current_path, filter_output_path)
+            if written is not None:
+                if written:
+                    print(f"Saved filtered sequences from {current_path.name} as {filter_output_path.name}")
+                else:
+                    print(f"No sequences found for the given {what} in {current_path.name}.")
+                continue
         result = model.predict_columnar(current_path, step=step)
         result.input_source = current_path.name
         if classification_output_path:

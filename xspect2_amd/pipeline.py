@@ -12,11 +12,15 @@ the data:
 
 Here one parse feeds both models.  Every batch of the native reader goes to
 the GPU once.  The genus probe runs there, and only its per-read hits and
-k-mer counts come back (12 B per read).  The keep decision is
-``round(h / n, 2) >= threshold`` (``result.py`` ``get_filter_mask``), made on
-the host with Python's own rounding over the batch's distinct (h, n) pairs.
-The kept reads are then compacted on the device (``xs_gather_reads_device``)
-and probed against the species bank.  Outputs are the reference's files, with
+k-mer counts come back for the genus JSON (12 B per read).  The keep decision
+is ``round(h / n, 2) >= threshold`` (``result.py`` ``get_filter_mask``), made
+on the device by comparison against the rounding cuts
+(``xs_filter_keep_device``); the kept reads' index and output offsets come
+from one scan there (``xs_filter_compact_device``), and the host learns how
+many reads and bytes were kept in the batch's one sync.  The kept reads are
+then gathered on the device (``xs_gather_reads_device``) and probed against
+the species bank.  ``keep_mask`` is the same decision on the host, for the
+by-id fallback and ``reference_pipeline``.  Outputs are the reference's files, with
 the same names and the same bytes:
 ``genus_classification_<run>.json``,
 ``filtered_sequences/genus_filtered_<run>.fasta`` and
@@ -30,7 +34,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .bank import gather_reads_device
+from .bank import filter_compact_device, filter_keep_device, gather_reads_device
 from .file_io import FASTA_ENDINGS, FASTQ_ENDINGS, prepare_input_output_paths, read_batches
 from .result import MatrixResult
 
@@ -125,6 +129,7 @@ def _fused_pass(path: Path, genus, species, threshold: float, step: int, fasta_o
     gcol, scol = _Collector(), _Collector()
     written = 0
     serr = None
+    pin = None
     for b in read_batches(path, batch_bytes, pinned=True):
         L = b.lengths()
         if (L <= genus.k).any():  # genus predict on every read (:224-225)
@@ -136,15 +141,33 @@ def _fused_pass(path: Path, genus, species, threshold: float, step: int, fasta_o
         d_gh = torch.empty(n, dtype=torch.int32, device=dev)
         d_gnk = torch.empty(n, dtype=torch.int64, device=dev)
         gbank.query_device(d_seq, nbytes, d_off, n, step, d_gh, d_gnk, None, stream=s)
-        gh = d_gh.cpu().numpy().view(np.uint32)
-        gnk = d_gnk.cpu().numpy().view(np.uint64)
+        # the keep decision and the hand-off stay on the device: keep bytes, then the kept reads' index,
+        # output offsets and counts (m, kept bytes) by one scan; a NaN threshold passes the reference's
+        # range check and keeps no read
+        d_idx = torch.empty(n, dtype=torch.int32, device=dev)
+        d_off2 = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        d_cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        if threshold == threshold:
+            d_keep = torch.empty(n, dtype=torch.uint8, device=dev)
+            filter_keep_device(d_gh, d_gnk, n, 1, 0, threshold, d_keep, stream=s)
+            filter_compact_device(d_keep, d_off, n, d_idx, d_off2, d_cnt, stream=s)
+        # one sync: the genus columns for the JSON, the counts and the index for the FASTA writer and the ids
+        # into one pinned block kept for the whole file: [counts | k-mer counts | hits | index]
+        if pin is None or pin.numel() < 16 + 16 * n:
+            pin = torch.empty(16 + 16 * n, dtype=torch.uint8, pin_memory=True)
+        h_cnt, h_gnk = pin[:16].view(torch.int64), pin[16:16 + 8 * n].view(torch.int64)
+        h_gh, h_idx = pin[16 + 8 * n:16 + 12 * n].view(torch.int32), pin[16 + 12 * n:16 + 16 * n].view(torch.int32)
+        for h, d in ((h_gh, d_gh), (h_gnk, d_gnk), (h_cnt, d_cnt), (h_idx, d_idx)):
+            h.copy_(d, non_blocking=True)
+        stream.synchronize()
+        gh = h_gh.numpy().view(np.uint32).copy()
+        gnk = h_gnk.numpy().view(np.uint64).copy()
         ids = b.ids()
         gcol.add(ids, gh.reshape(n, 1), gnk)
-        keep = keep_mask(gh, gnk, threshold)
-        idx = np.flatnonzero(keep).astype(np.uint32)
-        m = int(idx.size)
+        m, mbytes = (int(v) for v in h_cnt.tolist())
         if not m:
             continue
+        idx = h_idx.numpy()[:m].view(np.uint32).copy()
         fasta_out.parent.mkdir(parents=True, exist_ok=True)
         b.write_fasta(fasta_out, idx, append=written > 0)
         written += m
@@ -152,11 +175,6 @@ def _fused_pass(path: Path, genus, species, threshold: float, step: int, fasta_o
             serr = _short_read_error()
         if serr is not None:
             continue
-        out_off = np.zeros(m + 1, dtype=np.uint64)
-        np.cumsum(L[idx], out=out_off[1:])
-        mbytes = int(out_off[-1])
-        d_idx = torch.from_numpy(idx.view(np.int32)).to(dev)
-        d_off2 = torch.from_numpy(out_off.view(np.int64)).to(dev)
         d_seq2 = torch.empty(max(mbytes, 1), dtype=torch.uint8, device=dev)
         gather_reads_device(d_seq, d_off, d_idx, m, d_seq2, d_off2, stream=s)
         d_sh = torch.empty((m, D), dtype=torch.int32, device=dev)

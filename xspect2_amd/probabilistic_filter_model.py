@@ -22,7 +22,7 @@ from ._lib import XS_BANK_COBS_CLASSIC
 from .file_io import (FASTA_ENDINGS, FASTQ_ENDINGS, FileShard, check_input_path, file_reader_device,
                       get_record_iterator, is_record, read_batches, seq_text)
 from .packing import PackedIds, PackedReads, pack_sequences
-from .result import MatrixResult, ModelResult
+from .result import FilterResult, MatrixResult, ModelResult
 from .util import default_device, slugify
 
 # One C-ABI call handles at most this many sequence bytes / reads.
@@ -282,6 +282,80 @@ class ProbabilisticFilterModel:
         ids, _, hits_m, nk = self._matrix(sequence_input, step)
         return MatrixResult(self.slug(), ids, self._labels(display_name), hits_m, nk,
                             sparse_sampling_step=step, doc_mask=self._doc_mask(exclude_ids))
+
+    def filter_target(self, label: str, threshold: float, exclude_ids=None):
+        """(doc column of `label`, doc mask or None) for a device filter call, or
+        the error ``get_filter_mask`` raises for these arguments (the threshold's
+        ValueError, ``KeyError(label)`` for an unknown or excluded label); None
+        where the device decision does not apply (equal labels collapse in the
+        reference's dictionaries)."""
+        if threshold < 0 and not threshold == -1 or threshold > 1:
+            return ValueError("The filter threshold must be between 0 and 1.")
+        if not threshold == threshold:
+            return None  # NaN passes the reference's range check and keeps no read
+        labels = self._labels(False)
+        if len(set(labels)) != len(labels):
+            return None
+        mask = self._doc_mask(exclude_ids)
+        col = next((d for d, name in enumerate(labels) if name == label and (mask is None or mask[d])), None)
+        return KeyError(label) if col is None else (col, mask)
+
+    def filter_columnar(self, sequence_input, label: str, threshold: float = 0.7, exclude_ids: list[str] = None,
+                        step: int = 1) -> FilterResult:
+        """Which reads pass the filter for `label` (``predict`` followed by
+        ``get_filtered_subsequence_labels``, reference ``result.py:92-149``), as a
+        FilterResult: the probe and the decision run on the device, one byte per
+        read comes back and the hit matrix never leaves HBM.  Same errors as
+        ``predict_columnar(...).get_filter_mask(label, threshold)``, in its order."""
+        if step < 1:
+            raise ValueError("step must be >= 1")
+        target = self.filter_target(label, threshold, exclude_ids)
+        if target is None:  # the reference's dictionaries decide
+            # one entry per distinct id, as the dictionaries hold them (the first position, the last
+            # record's values); label_hits is the first doc column carrying the label
+            res = self.predict_columnar(sequence_input, exclude_ids, step)
+            mask = res.get_filter_mask(label, threshold)
+            row = {rid: i for i, rid in enumerate(res.ids)}
+            rows = np.array([row[rid] for rid in mask], dtype=np.int64)
+            col = next(d for d in res.docs.tolist() if res.labels[d] == label)
+            return FilterResult(self.slug(), list(mask), label, threshold,
+                                np.fromiter(mask.values(), np.uint8, len(mask)),
+                                res.hits[rows, col].astype(np.uint32), res.num_kmers[rows], step)
+        part, parts = 0, 1
+        if isinstance(sequence_input, FileShard):
+            sequence_input, part, parts = sequence_input.path, sequence_input.part, sequence_input.parts
+        if isinstance(sequence_input, Path):
+            check_input_path(sequence_input)
+            if self.index is None:
+                raise ValueError("The model has not been trained yet")
+            ids, out = [], []
+            for batch in read_batches(sequence_input, part=part, parts=parts, pinned=True):
+                if (batch.lengths() <= self.k).any():
+                    raise ValueError("Invalid sequence, must be longer than k")
+                if not isinstance(target, Exception):
+                    out.append(self.index.query_keep(batch.packed, target[0], threshold, step, target[1])[:3])
+                ids.append(batch.ids_packed())
+            ids = PackedIds.concat(ids) if ids else []
+        else:
+            records = self._collect(sequence_input)
+            ids = [r.id for r in records]
+            texts = [seq_text(r.seq) for r in records]
+            lens = [len(t) for t in texts]
+            if any(not n > self.k for n in lens):
+                raise ValueError("Invalid sequence, must be longer than k")
+            if self.index is None:
+                raise ValueError("The model has not been trained yet")
+            out = [] if isinstance(target, Exception) else [
+                self.index.query_keep(pack_sequences(texts[lo:hi]), target[0], threshold, step, target[1])[:3]
+                for lo, hi in _batches(lens)]
+        if isinstance(target, ValueError):
+            raise target
+        if not len(ids):
+            raise IndexError("list index out of range")  # get_scores on no reads, as the reference
+        if isinstance(target, KeyError):
+            raise target
+        keep, hits, nk = (np.concatenate(col) for col in zip(*out))
+        return FilterResult(self.slug(), ids, label, threshold, keep, hits, nk, step)
 
     def predict(self, sequence_input, exclude_ids: list[str] = None, step: int = 1,
                 display_name: bool = False, validation: bool = False) -> ModelResult:

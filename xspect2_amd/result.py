@@ -316,6 +316,55 @@ class MatrixResult:
                             meta["sparse_sampling_step"], meta["prediction"], meta["input_source"], z["doc_mask"])
 
 
+class FilterResult:
+    """The per-read answer of a filter call (``filter_columnar``): one keep byte
+    per read, decided on the device, with the label's hit count and the read's
+    k-mer count.  It stands for ``ModelResult.get_filter_mask`` /
+    ``get_filtered_subsequence_labels`` (``result.py:92-149``) of one label and
+    threshold, without the hit matrix: 13 bytes per read in place of a row.
+
+    ``ids`` may be a ``PackedIds`` (the reader's id buffer).  ``kept_ids()``
+    collapses repeated ids as the reference's dictionaries do (the first
+    position, the last record's decision) and leaves out a read called
+    "misclassified" (popped from the hits, ``result.py:43``)."""
+
+    def __init__(self, model_slug: str, ids: list[str] | PackedIds, label: str, threshold: float, keep: np.ndarray,
+                 label_hits: np.ndarray, num_kmers: np.ndarray, sparse_sampling_step: int = 1,
+                 input_source: str | None = None):
+        self.model_slug = model_slug
+        self.ids = ids if isinstance(ids, PackedIds) else list(ids)
+        self.label = label
+        self.threshold = threshold
+        self.keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        self.label_hits = np.ascontiguousarray(label_hits, dtype=np.uint32)
+        self.num_kmers = np.ascontiguousarray(num_kmers, dtype=np.uint64)
+        n = len(self.ids)
+        if not (self.keep.shape == self.label_hits.shape == self.num_kmers.shape == (n,)):
+            raise ValueError("keep, label_hits and num_kmers must be [len(ids)]")
+        self.sparse_sampling_step = sparse_sampling_step
+        self.input_source = input_source
+
+    def __len__(self) -> int:
+        return len(self.ids)
+
+    def kept_index(self) -> np.ndarray:
+        """Positions of the kept reads, ascending (uint32)."""
+        return np.flatnonzero(self.keep).astype(np.uint32)
+
+    def get_filter_mask(self) -> dict[str, bool]:
+        mask = dict(zip(self.ids, self.keep.astype(bool).tolist()))  # a repeated id: first position, last value
+        mask.pop("misclassified", None)
+        return mask
+
+    def kept_ids(self) -> list[str]:
+        """``get_filtered_subsequence_labels(label, threshold)`` of the reference."""
+        packed = isinstance(self.ids, PackedIds)
+        if (self.ids.has_duplicates() if packed else len(set(self.ids)) != len(self.ids)) or "misclassified" in self.ids:
+            return [rid for rid, keep in self.get_filter_mask().items() if keep]
+        ids = self.ids
+        return [ids[i] for i in np.flatnonzero(self.keep).tolist()]
+
+
 class MlstResult:
     """MLST strain-type results (mirror of ``src/xspect/models/mlst_result.py:7-62``)."""
 
