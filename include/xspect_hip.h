@@ -149,7 +149,14 @@ int xs_bank_create_bloom(int device, uint32_t term_size, uint64_t nbytes, uint32
  * rec_doc[r] (ignored for rbloom; may be NULL there). */
 int xs_bank_build(xs_bank* bank, const char* seqs, const uint64_t* offsets,
                   const uint32_t* rec_doc, uint64_t n_rec);
-/* Same with device-resident buffers, enqueued on `stream` (NULL = the null stream). */
+/* Same with device-resident buffers, enqueued on `stream` (NULL = the null stream).
+ * A rec_doc entry >= num_docs: xs_bank_build reads the entries on the host and
+ * refuses the whole call (XS_ERR_ARG, the image unchanged); here they are in
+ * device memory and no entry is read back, so such a record is skipped (none
+ * of its k-mers is inserted, no byte outside the image is touched) and every
+ * other record of the call is inserted; the call returns XS_OK.  Both calls
+ * OR into the image they find: building twice, or over an uploaded image,
+ * accumulates. */
 int xs_bank_build_device(xs_bank* bank, const void* d_seqs, uint64_t seq_bytes,
                          const uint64_t* d_offsets, const uint32_t* d_rec_doc, uint64_t n_rec,
                          void* stream);
@@ -158,7 +165,13 @@ int xs_bank_save(xs_bank* bank, const char* path);
 /* Copy the bank back in FILE layout (rows of page_size bytes, groups in order;
  * rbloom: the raw bit bytes). nbytes must equal the file payload size. */
 int xs_bank_download(xs_bank* bank, void* host, uint64_t nbytes);
-/* Replace the bank image from a FILE-layout payload (the inverse of download). */
+/* Replace the bank image from a FILE-layout payload (the inverse of download).
+ * Padding bits, the bits of docs >= num_docs in the last byte of a classic row
+ * and in the unused tail of a compact bank's last group, are accepted as they
+ * come and ignored: a file of another writer may have them set.  No query
+ * reports a doc >= num_docs or lets such a bit into a count, a total or a best
+ * doc; download and save give the bytes back unchanged, padding included.  The
+ * builders never set a padding bit. */
 int xs_bank_upload(xs_bank* bank, const void* host, uint64_t nbytes);
 
 /* rbloom files carry no k-mer length (XspecT keeps it in the model JSON,
